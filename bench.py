@@ -7,10 +7,13 @@ iteration = RK4 linearisation + Riccati IPM QP + full step, post-solve command) 
 harness kernel that advances the plant one RK4 step and regenerates the path references.
 value = (instances x steps, all ranks) / max-over-ranks wall time of the timed region.
 
-Also reported: the u0 max-abs error against the fp64 CPU oracle on identical inputs,
-the executed IPM iterations, the roofline of the dominant kernel (algorithmic FLOPs from the SURVEY
-formula / HIP-event kernel time; FP32 peak 157.3 TF/s), and the CPU baseline (the oracle, OpenMP on
-the host cores, on a bounded sample of the same workload, rank 0 at N=1 only).
+A plain run sets up, warms up, times the steps and prints the line (headline figure, executed IPM iterations,
+failed solves); --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.
+
+With --full also reported: the u0 max-abs error against the fp64 CPU oracle on identical inputs,
+the roofline of the dominant kernel (algorithmic FLOPs from the SURVEY formula / HIP-event kernel time; FP32
+peak 157.3 TF/s), and the CPU baseline (the oracle, OpenMP on the host cores, on a bounded sample of the same
+workload, rank 0 at N=1 only).
 """
 import argparse
 import json
@@ -295,6 +298,44 @@ class LaunchTimer:
         return [max(s[0].elapsed_time(b) for b in e) for s, e in self.ev]
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files of a run together
+DUMP_SAMPLE_SEED = 20250824
+
+
+def step_outputs(fleets):
+    """What a caller of the timed step (FleetNode.step) holds after it, per fleet f<j>_<model>: the solve's
+    outputs (u0, cmd, status, qp_iter), the iterate it left in the handle (xbar, ubar, robots in the last axis)
+    and the plant / reference step's outputs the next tick reads (pose, vel, steer, traj, tlen). Host arrays,
+    float32 (the device's own precision; the integer arrays are exact in it)."""
+    out = {}
+    for j, f in enumerate(fleets):
+        xv, uv, _ = f.solver.state()
+        arrs = dict(u0=f.u0, cmd=f.cmd, status=f.status, qp_iter=f.qp_iter, xbar=xv.to_tensor()[:, :f.B],
+                    ubar=uv.to_tensor()[:, :f.B], pose=f.pose, vel=f.vel, steer=f.steer, traj=f.traj, tlen=f.tlen)
+        for k, a in arrs.items():
+            if a is not None:
+                out[f"f{j}_{f.model}_{k}"] = np.ascontiguousarray(a.detach().cpu().numpy(), np.float32)
+    return out
+
+
+def dump_outputs(path, fleets, rank=0, world=1, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: step_outputs() as <path>/<name>.npy (ranks of a multi-GPU run add _rank<r>). Over the
+    byte budget every array keeps the same fixed, seeded sample of each fleet's robots (its last axis)."""
+    arrs = step_outputs(fleets)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > budget:
+        keep = max(0.0, budget - 256 * len(arrs)) / total  # (room for the .npy headers)
+        for j, f in enumerate(fleets):
+            n = max(1, int(f.B * keep))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED + j).choice(f.B, n, replace=False))
+            for k in [k for k in arrs if k.startswith(f"f{j}_")]:
+                arrs[k] = np.ascontiguousarray(arrs[k][..., idx])
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+    return sorted(arrs)
+
+
 def _free_port():
     import socket
     with socket.socket() as so:
@@ -360,7 +401,13 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="robots per model replayed on the CPU oracle (0: the whole batch)")
     ap.add_argument("--cpu-ticks", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle replay")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what takes work of its own: the roofline record (HIP events around every solve "
+                         "launch of the timed steps) and, unless --no-cpu-baseline, the CPU baseline and the u0 error "
+                         "against the fp64 oracle; a plain run leaves those fields null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (step_outputs) as DIR/<name>.npy")
     ap.add_argument("--gather", action="store_true", help="all-gather u0+status to rank 0 every tick (RCCL)")
     ap.add_argument("--dist", action="store_true",
                     help="initialise the RCCL process group at world size 1 too (exercises the barrier, the MAX "
@@ -437,13 +484,16 @@ def main():
     # timer around every solve launch). One stream: the solve's duration. Joined streams: from one start event
     # on the main stream to each stream's end-of-solve event (the region = the latest). Decoupled streams: each
     # launch from its own stream's start event.
-    timer = None if cpu else LaunchTimer(len(fleets), args.steps)
+    # --full only: a plain run records no events in its timed steps
+    timer = LaunchTimer(len(fleets), args.steps) if args.full and not cpu else None
     with TimedRegion(dev) as region:
         for k in range(args.steps):
             if timer is not None:
                 timer.k = k
             node.step(timer)
     elapsed = region.elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fleets, rank, world)
 
     kernel_ms = timer.kernel_ms(node.decoupled) if timer is not None else None
     its = node.iter_stats()
@@ -454,10 +504,11 @@ def main():
 
     result = None
     if rank == 0:
-        roof = roofline(fleets, node, kernel_ms, args.steps, step_s=elapsed / args.steps) if not cpu else None
+        roof = (roofline(fleets, node, kernel_ms, args.steps, step_s=elapsed / args.steps)
+                if timer is not None else None)
         cpu_base = None
         u0_err = None
-        if not args.no_cpu_baseline and world == 1 and not cpu:
+        if args.full and not args.no_cpu_baseline and world == 1 and not cpu:
             nthreads = int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1))
             cpu_rate, u0_err, nf, ns, rate_1, u0_err_acados = cpu_baseline(fleets, args.cpu_sample, args.cpu_ticks,
                                                                            nthreads)
@@ -484,7 +535,7 @@ def main():
                        "ranks": ranks, "backend": backend,
                        "launcher": os.environ.get("NMPC_BENCH_LAUNCHER",
                                                   "torchrun" if "WORLD_SIZE" in os.environ else "single process"),
-                       "closed_loop_warmup_ticks": args.closed_loop_warmup, "rccl_gather": gather,
+                       "closed_loop_warmup_ticks": args.closed_loop_warmup, "rccl_gather": gather, "full": args.full,
                        "ipm_rules": args.ipm_rules + (f" + {args.qp}" if args.qp else "")},
             "u0_max_abs_err": u0_err, "qp_iter_mean": round(k_mean, 3), "qp_iter_max": int(node.iters_max.max().item()),
             "qp_iter": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in its.items()},

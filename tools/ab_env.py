@@ -30,8 +30,8 @@ def main():
                 env = dict(os.environ, **kv)
                 path = os.path.join(OUT, f"{tag}_{c}_{name}_{rep}.json")
                 with open(path, "w") as fh:
-                    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", c, "--steps", "60",
-                                        "--no-cpu-baseline"], stdout=fh, stderr=subprocess.DEVNULL, env=env,
+                    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", c,
+                                        "--steps", "60", "--no-cpu-baseline"], stdout=fh, stderr=subprocess.DEVNULL, env=env,
                                        timeout=300)
                 if r.returncode != 0:
                     print(f"STOP {c} {name} rc={r.returncode}")
