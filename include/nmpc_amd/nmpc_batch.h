@@ -149,6 +149,29 @@ int nmpc_batch_run_path(nmpc_batch* b, int B, const float* pose, const float* ve
                         double sample_period, int is_holonomic, const unsigned char* reset, float* traj_out,
                         float* cmd, float* u0, int* status, int* qp_iter, float* qp_res, void* stream);
 
+/* The whole FollowPath tick (NMPCNavControlROS.cpp:648-698 -> :713) from the measured pose to the command:
+ * nmpc_path_nearest (nmpc_path.h: processNearestPoint and the path errors, :650-657), then nmpc_batch_run_path
+ * from that parameter, then the path-error check (:658-664). Three launches on `stream`, no host synchronisation.
+ *   path_u   [B] in: lower bound of the nearest-point search, the robot's progress so far (0 on a new path; the
+ *            node pops the segments behind the robot, :603-609, so its search never goes back either);
+ *            out: nearest_u, which is also next tick's bound
+ *   max_pos_err, max_ori_err  max_pos_error_to_path_ / max_ori_error_to_path_; a robot with pos_err >= max_pos_err
+ *            or ori_err >= max_ori_err (:658-659) is off its path: off_path[i] = 1 and cmd[:, i] = 0, the stop
+ *            command of :660. +inf or NaN switches a comparison off (enable_safe_conditions_ = false: both)
+ *   err      [2][B] {pos_error_to_path, ori_error_to_path} or NULL; the heading of the orientation error is the
+ *            holonomic one when the handle's model is omni4 (:654), whatever is_holonomic says: that flag is the
+ *            discretizer's, and the node passes false there for every model (:666)
+ *   off_path [B] or NULL
+ * Everything else as nmpc_batch_run_path. One departure from the node: it skips the solve of an off-path robot
+ * (:663); here that robot's solve still runs (its iterate and carried refs advance) and only its command is
+ * stopped. The node then waits for a new goal, which resets the controller anyway: pass reset[i] = 1 with it.
+ * sample_period must be finite here. */
+int nmpc_batch_follow_path(nmpc_batch* b, int B, const float* pose, const float* vel, const float* steer,
+                           const nmpc_path_segment* segs, int seg_stride, const int* nseg, double* path_u,
+                           double sample_period, int is_holonomic, double max_pos_err, double max_ori_err,
+                           const unsigned char* reset, double* err, unsigned char* off_path, float* traj_out,
+                           float* cmd, float* u0, int* status, int* qp_iter, float* qp_res, void* stream);
+
 /* Kernel variant: NMPC_KERNEL_TEAM (16-lane team per robot, DPP row exchange) is the only one; any other value
  * returns NMPC_ERR_UNSUPPORTED. (The round-1 one-lane-per-robot kernel was removed: its fp32 factor is not
  * accurate enough at bench scale, DESIGN.md "Algorithm and precision".) */

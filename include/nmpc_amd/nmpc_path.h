@@ -50,6 +50,37 @@ int nmpc_path_discretize(int B, const nmpc_path_segment* segs, int seg_stride, c
                          const double* nearest_u, double sample_period, int num_poses, int is_holonomic,
                          float* traj, double* traj64, void* stream);
 
+/* Each robot's nearest path point: the step that produces nearest_u, processNearestPoint (NMPCNavControlROS.cpp:
+ * 597-610) with the path errors of :654-657, for robots [0, B) in one launch.
+ *
+ * The reference calls TPathProcessMinDist(10, 0.01)::GetMinDist of parametric_trajectories_common, which it does
+ * not vendor: that search's tolerance and tie rule cannot be read. The search rule here is THIS PROJECT'S OWN:
+ *   path parameter U in [0, n], n = nseg[i]; segment k = min(floor(U), n-1), local parameter u = U - k;
+ *   P(U) = (GetX(u), GetY(u)) of segment k; r = (pose x, pose y) widened from fp32 exactly
+ *   search range [lo, hi]: [0, n] without u_range, else u_range's bounds clamped into [0, n]; a NaN bound leaves
+ *     that side open; lo > hi is read as hi = lo
+ *   nearest_u = the U in range that minimises |P(U) - r| in fp64: |P(nearest_u) - r| <= d_min + 1e-9 m on
+ *     metre-scale paths (measured 1e-15); ties go to the smallest U; the same inputs give the same bits whatever
+ *     B and the robot's slot.
+ * Arguments:
+ *   segs, seg_stride, nseg  as nmpc_path_discretize (an nseg[i] above seg_stride is read as seg_stride)
+ *   pose       [3][B] float {x, y, theta}
+ *   u_range    [2][B] {lo, hi} or NULL
+ *   holonomic_heading  heading of the orientation error: != 0 theta_holonomic (the node: omni4, :654), 0 theta,
+ *              plus pi when the segment of nearest_u has v < 0 (:655)
+ * outputs:
+ *   nearest_u  [B]
+ *   near       [4][B] {x, y, theta, theta_holonomic} at nearest_u or NULL: GetMinDist's raw outputs, theta =
+ *              atan2(GetDY, GetDX) without the reverse-driving pi
+ *   err        [2][B] {pos_error_to_path, ori_error_to_path} or NULL: sqrt(dx^2 + dy^2) and
+ *              |normAngRad(heading - pose theta)| (:656-657, utils.h:41-47)
+ * Undefined inputs: a NaN (or infinite) pose or coefficient gives nearest_u = lo and err = NaN; nseg[i] < 1 gives
+ * nearest_u = 0, near = err = NaN and reads no segment; a segment whose derivative is zero everywhere is one
+ * candidate point. No loop depends on the data. */
+int nmpc_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg, const float* pose,
+                      const double* u_range, int holonomic_heading, double* nearest_u, double* near, double* err,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,6 +227,30 @@ class BatchSolver:
             _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)),
             "nmpc_batch_run_path")
 
+    def follow_path(self, pose, vel, segs, nseg, path_u, sample_period, is_holonomic=False, max_pos_err=float("inf"),
+                    max_ori_err=float("inf"), steer=None, reset=None, err=None, off_path=None, traj_out=None, cmd=None,
+                    u0=None, status=None, qp_iter=None, qp_res=None, stream=None):
+        """The whole FollowPath tick on the device (nmpc_batch_follow_path): nearest path point, getNextNPoses +
+        run from it, path-error check. path_u float64 [B] is read as the lower bound of the search (the robot's
+        progress so far; 0 on a new path) and overwritten with nearest_u; err float64 [2][B] receives
+        {pos_error_to_path, ori_error_to_path}, off_path uint8 [B] the robots whose error reached max_pos_err /
+        max_ori_err (their cmd is zeroed; inf or NaN: no check). Everything else as run_path."""
+        B = pose.shape[1]
+        if not 0 <= B <= self.capacity:
+            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        if segs.dim() != 3 or segs.shape[0] != B or segs.shape[2] != 16:
+            raise ValueError(f"segs: expected shape ({B}, S, 16), got {tuple(segs.shape)}")
+        check(lib().nmpc_batch_follow_path(
+            self._h, B, _ptr(pose, F32, (3, B), "pose"), _ptr(vel, F32, (3, B), "vel"),
+            _ptr(steer, F32, (B,), "steer"), _ptr(segs, torch.float64, None, "segs"), segs.shape[1],
+            _ptr(nseg, I32, (B,), "nseg"), _ptr(path_u, torch.float64, (B,), "path_u"), float(sample_period),
+            1 if is_holonomic else 0, float(max_pos_err), float(max_ori_err), _ptr(reset, U8, (B,), "reset"),
+            _ptr(err, torch.float64, (2, B), "err"), _ptr(off_path, U8, (B,), "off_path"),
+            _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"), _ptr(cmd, F32, (3, B), "cmd"),
+            _ptr(u0, F32, (self.nu, B), "u0"), _ptr(status, I32, (B,), "status"),
+            _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)),
+            "nmpc_batch_follow_path")
+
     def fleet_sim_step(self, path, s, pose, vel, steer, u0, status, traj, traj_len, advance=True, stream=None):
         B = pose.shape[1]
         if not 0 <= B <= self.capacity:

@@ -49,6 +49,8 @@ struct nmpc_batch {
     // the team kernel's single-direction record layout (NMPC_REC_WIDE / NMPC_REC_SPLIT), fixed per handle: resolved
     // at create time from this handle alone and changed only by nmpc_batch_set_record_layout
     int rec_split = 0;
+    double* path_err = nullptr;  // [2][capacity] path errors of nmpc_batch_follow_path when the caller keeps none
+                                 // (allocated at the first such call)
 #ifdef NMPC_HYBRID
     // hybrid launch (A/B build only, -DNMPC_HYBRID, NMPC_AMD_HYBRID=H): in a team-kernel launch the robots whose last
     // IPM count was >= H (at most hybrid_cap of them, the hardest first) run the segmented row-parallel kernel (one
@@ -340,6 +342,19 @@ __global__ void k_forget_warm(unsigned char* warm, const unsigned char* mask, in
     if (i < B && (!mask || mask[i])) warm[i] = 0;
 }
 
+// the path-error check of a FollowPath tick (NMPCNavControlROS.cpp:658-660): a robot whose position or orientation
+// error reaches its threshold is flagged and gets the stop command; use_pos / use_ori: the comparison is on
+__global__ void k_path_guard(int B, const double* err, double max_pos, double max_ori, int use_pos, int use_ori,
+                             unsigned char* off_path, float* cmd)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const bool off = (use_pos && err[i] >= max_pos) || (use_ori && err[(size_t)B + i] >= max_ori);
+    if (off_path) off_path[i] = off ? 1 : 0;
+    if (off && cmd)
+        for (int j = 0; j < 3; j++) cmd[(size_t)j * B + i] = 0.0f;
+}
+
 int check_params(const nmpc_model_params* prm)
 {
     int nx, nu, nbx, nbu, np;
@@ -557,6 +572,7 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->order);
     (void)hipFree(b->sorted);
     (void)hipFree(b->warm);
+    (void)hipFree(b->path_err);
 #ifdef NMPC_HYBRID
     (void)hipFree(b->hyb_n);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
@@ -769,6 +785,46 @@ int nmpc_batch_run_path(nmpc_batch* b, int B, const float* pose, const float* ve
     return hip_err(launch(b, a, kModeRun, (hipStream_t)stream), "run_path launch");
 }
 
+int nmpc_batch_follow_path(nmpc_batch* b, int B, const float* pose, const float* vel, const float* steer,
+                           const nmpc_path_segment* segs, int seg_stride, const int* nseg, double* path_u,
+                           double sample_period, int is_holonomic, double max_pos_err, double max_ori_err,
+                           const unsigned char* reset, double* err, unsigned char* off_path, float* traj_out,
+                           float* cmd, float* u0, int* status, int* qp_iter, float* qp_res, void* stream)
+{
+    const TraceRange trace("nmpc_batch_follow_path");
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (B == 0) return NMPC_OK;
+    if (!pose || !vel || !segs || !nseg || !path_u)
+        return set_err(NMPC_ERR_ARG, "pose, vel, segs, nseg and path_u are required");
+    if (seg_stride < 1) return set_err(NMPC_ERR_ARG, "seg_stride < 1");
+    if (!std::isfinite(sample_period) || sample_period < 0.0)
+        return set_err(NMPC_ERR_ARG, "sample_period must be finite and >= 0");
+    // a threshold of +inf or NaN switches its comparison off
+    const int use_pos = !(std::isnan(max_pos_err) || max_pos_err == INFINITY);
+    const int use_ori = !(std::isnan(max_ori_err) || max_ori_err == INFINITY);
+    const bool guard = use_pos || use_ori || off_path;
+    if (guard && !err) {
+        if (!b->path_err) {
+            const hipError_t e = hipMalloc(&b->path_err, sizeof(double) * 2 * (size_t)b->capacity);
+            if (e != hipSuccess) return hip_err(e, "hipMalloc");
+        }
+        err = b->path_err;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // the search starts at the robot's progress so far and writes nearest_u over it
+    int rc = hip_err(launch_path_nearest(B, segs, seg_stride, nseg, pose, path_u, nullptr,
+                                         b->prm.model == NMPC_MODEL_OMNI4AMR ? 1 : 0, path_u, nullptr, err, s),
+                     "path_nearest launch");
+    if (rc) return rc;
+    rc = nmpc_batch_run_path(b, B, pose, vel, steer, segs, seg_stride, nseg, path_u, sample_period, is_holonomic,
+                             reset, traj_out, cmd, u0, status, qp_iter, qp_res, stream);
+    if (rc || !guard) return rc;
+    hipLaunchKernelGGL(k_path_guard, dim3((B + 255) / 256), dim3(256), 0, s, B, err, max_pos_err, max_ori_err, use_pos,
+                       use_ori, off_path, cmd);
+    return hip_err(hipGetLastError(), "path_guard launch");
+}
+
 int nmpc_batch_set_kernel(nmpc_batch* b, int kernel)
 {
     if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
@@ -936,6 +992,21 @@ int nmpc_path_discretize(int B, const nmpc_path_segment* segs, int seg_stride, c
     return hip_err(launch_path_discretize(B, segs, seg_stride, nseg, nearest_u, sample_period, num_poses,
                                           is_holonomic ? 1 : 0, traj, traj64, (hipStream_t)stream),
                    "path_discretize launch");
+}
+
+int nmpc_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg, const float* pose,
+                      const double* u_range, int holonomic_heading, double* nearest_u, double* near, double* err,
+                      void* stream)
+{
+    const TraceRange trace("nmpc_path_nearest");
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B < 0");
+    if (B == 0) return NMPC_OK;
+    if (!segs || !nseg || !pose) return set_err(NMPC_ERR_ARG, "segs, nseg and pose are required");
+    if (!nearest_u) return set_err(NMPC_ERR_ARG, "nearest_u is required");
+    if (seg_stride < 1) return set_err(NMPC_ERR_ARG, "seg_stride < 1");
+    return hip_err(launch_path_nearest(B, segs, seg_stride, nseg, pose, u_range, u_range ? u_range + B : nullptr,
+                                       holonomic_heading ? 1 : 0, nearest_u, near, err, (hipStream_t)stream),
+                   "path_nearest launch");
 }
 
 }  // extern "C"

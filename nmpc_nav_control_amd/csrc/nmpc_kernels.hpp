@@ -118,5 +118,10 @@ hipError_t launch_hybrid_order(const int* key, int B, int H, int cap, int* order
 hipError_t launch_path_discretize(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
                                   const double* nearest_u, double period, int num_poses, int holo, float* traj,
                                   double* traj64, hipStream_t stream);
+// nearest path point of every robot (path_nearest.hip): lo / hi [B] bounds of the search range, each may be nullptr;
+// lo may alias nearest_u (a robot's bound is read before its result is written)
+hipError_t launch_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
+                               const float* pose, const double* lo, const double* hi, int holo, double* nearest_u,
+                               double* near, double* err, hipStream_t stream);
 
 }  // namespace nmpc

@@ -3,6 +3,8 @@
 Mirrors include/nmpc_nav_control/PathDiscretizer.h:12-51 (constructor arguments, getNextNPoses) on top of
 ``nmpc_path_discretize`` (include/nmpc_amd/nmpc_path.h). The march itself runs only in the HIP kernel
 (csrc/path_discretizer.hip); this module builds and packs path segments and owns the device buffers.
+``nearest`` / ``PathMinDist`` are the step before it, each robot's nearest path point (``nmpc_path_nearest``,
+csrc/path_nearest.hip), by this project's own search rule: the reference's lives in the same un-vendored library.
 
 Path segments restate the part of parametric_trajectories_common::TPath that PathDiscretizer uses (the
 library is not vendored by the reference): cubic polynomials x(u), y(u), theta_h(u) on u in [0, 1] plus a
@@ -114,6 +116,48 @@ def discretize(segs, nseg, nearest_u, sample_period, num_poses, is_holonomic=Fal
                                      _dev_ptr(traj64, torch.float64), ctypes.c_void_p(s.cuda_stream)),
           "nmpc_path_discretize")
     return traj
+
+
+def nearest(segs, nseg, pose, u_range=None, holonomic_heading=False, near=None, err=None, stream=None):
+    """nmpc_path_nearest on device tensors: segs float64 [B][S][16], nseg int32 [B], pose float32 [3][B],
+    u_range float64 [2][B] {lo, hi} or None (the whole path; a NaN bound leaves its side open). Writes, if given,
+    near float64 [4][B] {x, y, theta, theta_holonomic} and err float64 [2][B] {pos_error_to_path,
+    ori_error_to_path}. Returns nearest_u float64 [B]. The search rule is this project's own (nmpc_path.h)."""
+    B, S = int(segs.shape[0]), int(segs.shape[1])
+    if segs.dim() != 3 or segs.shape[2] != SEG_DOUBLES:
+        raise ValueError("segs must be [B][S][16]")
+    if nseg.shape != (B,) or tuple(pose.shape) != (3, B):
+        raise ValueError("nseg must be [B] and pose [3][B]")
+    for t, rows, name in ((u_range, 2, "u_range"), (near, 4, "near"), (err, 2, "err")):
+        if t is not None and tuple(t.shape) != (rows, B):
+            raise ValueError(f"{name} must be [{rows}][B]")
+    nearest_u = torch.empty(B, dtype=torch.float64, device=segs.device)
+    s = stream if stream is not None else torch.cuda.current_stream(segs.device)
+    check(lib().nmpc_path_nearest(B, _dev_ptr(segs, torch.float64), S, _dev_ptr(nseg, torch.int32),
+                                  _dev_ptr(pose, torch.float32), _dev_ptr(u_range, torch.float64),
+                                  1 if holonomic_heading else 0, _dev_ptr(nearest_u, torch.float64),
+                                  _dev_ptr(near, torch.float64), _dev_ptr(err, torch.float64),
+                                  ctypes.c_void_p(s.cuda_stream)), "nmpc_path_nearest")
+    return nearest_u
+
+
+class PathMinDist:
+    """One-robot mirror of the call NMPCNavControlROS.cpp:599-601 makes, TPathProcessMinDist::GetMinDist, on the
+    device search (nmpc_path_nearest). The reference's constructor arguments (10, 0.01) belong to the un-vendored
+    library's own search and are accepted and ignored: the search rule is this project's."""
+
+    def __init__(self, num_iterations=10, tolerance=0.01, device="cuda"):
+        self.device = torch.device(device)
+
+    def GetMinDist(self, path_list, x, y, theta):
+        """(u, x, y, theta, theta_holonomic) of the path point nearest to the robot at (x, y)."""
+        segs, nseg = pack_paths([list(path_list)])
+        dev = self.device
+        near = torch.empty((4, 1), dtype=torch.float64, device=dev)
+        pose = torch.tensor([[x], [y], [theta]], dtype=torch.float32, device=dev)
+        u = nearest(torch.from_numpy(segs).to(dev), torch.from_numpy(nseg).to(dev), pose, near=near)
+        n = near.cpu().numpy()[:, 0]
+        return float(u.cpu()[0]), float(n[0]), float(n[1]), float(n[2]), float(n[3])
 
 
 class PathDiscretizer:

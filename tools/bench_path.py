@@ -3,10 +3,16 @@
 (lines and cubic Beziers, 1-4 segments per robot), N+1 = 41 poses per robot at dt = 1/40 s, inputs resident in
 HBM. Prints one JSON line: robots/s, ms per launch (HIP events on the launch stream), bytes moved per launch.
 
-With --tick: a whole path-following tick of diff robots (N = num_poses - 1), the two-launch form
-(nmpc_path_discretize + nmpc_batch_run) against the one-launch nmpc_batch_run_path, ms per tick each.
+With --nearest: the nearest-point search (nmpc_path_nearest) on the same paths, one JSON line of the same form,
+with the discretize launch timed in the same process next to it.
 
-usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--tick]
+With --tick: a whole path-following tick of diff robots (N = num_poses - 1), the two-launch form
+(nmpc_path_discretize + nmpc_batch_run) against the one-launch nmpc_batch_run_path and against
+nmpc_batch_follow_path (nearest point + run_path + path-error check), ms per tick each.
+
+Poses of --nearest and --tick: the path points at the seeded nearest_u, displaced by a seeded offset of up to 0.1 m.
+
+usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick]
 """
 import argparse
 import json
@@ -45,13 +51,69 @@ def seeded_paths(B, max_segs=4, seed=20250824):
     return segs, nseg, nearest_u
 
 
+def seeded_poses(segs, nseg, nearest_u, seed=20250825):
+    """[3][B] float32: each robot at the point of its path at nearest_u, moved by up to 0.1 m per axis"""
+    rng = np.random.default_rng(seed)
+    B = len(nseg)
+    k = np.minimum(np.floor(nearest_u).astype(int), nseg - 1)
+    u = nearest_u - k
+    c = segs[np.arange(B), k]
+    pw = np.stack([u ** 0, u, u ** 2, u ** 3], 1)
+    x, y = (c[:, 0:4] * pw).sum(1), (c[:, 4:8] * pw).sum(1)
+    dx, dy = (c[:, 1:4] * pw[:, :3] * [1, 2, 3]).sum(1), (c[:, 5:8] * pw[:, :3] * [1, 2, 3]).sum(1)
+    off = rng.uniform(-0.1, 0.1, (2, B))
+    return np.stack([x + off[0], y + off[1], np.arctan2(dy, dx)]).astype(np.float32)
+
+
+def timed(fn, iters, stream):
+    """ms per call of fn: 5 warm-up calls, then `iters` calls between two HIP events on the launch stream"""
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(iters):
+        fn()
+    e1.record(stream)
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def nearest_bench(a):
+    from nmpc_nav_control_amd.path import nearest
+    dev = torch.device("cuda:0")
+    segs, nseg, nu = seeded_paths(a.B)
+    S, NS, U = (torch.from_numpy(x).to(dev) for x in (segs, nseg, nu))
+    P = torch.from_numpy(seeded_poses(segs, nseg, nu)).to(dev)
+    err = torch.empty((2, a.B), dtype=torch.float64, device=dev)
+    traj = torch.empty((a.num_poses, 3, a.B), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream()
+    # three interleaved rounds of both launches in one process; the median of each
+    ms_n, ms_d = [], []
+    for _ in range(3):
+        ms_n.append(timed(lambda: nearest(S, NS, P, err=err), a.iters, stream))
+        ms_d.append(timed(lambda: discretize(S, NS, U, 1 / 40, a.num_poses, traj=traj), a.iters, stream))
+    ms, msd = sorted(ms_n)[1], sorted(ms_d)[1]
+    # compulsory bytes: the segment records, nseg and the pose in, nearest_u and the two errors out
+    nbytes = int(nseg.sum()) * SEG_DOUBLES * 8 + a.B * (4 + 12) + a.B * 3 * 8
+    print(json.dumps(dict(metric="nearest path point robots/s", value=round(a.B / (ms * 1e-3), 1), B=a.B,
+                          ms_per_launch=round(ms, 4), ms_rounds=[round(m, 4) for m in ms_n],
+                          discretize_ms_per_launch=round(msd, 4), num_poses=a.num_poses,
+                          bytes_per_launch=nbytes, achieved_GBs=round(nbytes / (ms * 1e-3) / 1e9, 2),
+                          bound="fp64 issue (16 lanes per robot: 16 samples + 8 Newton steps per segment)")),
+          flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=4096)
     ap.add_argument("--num-poses", type=int, default=41)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--tick", action="store_true")
+    ap.add_argument("--nearest", action="store_true")
     a = ap.parse_args(argv)
+    if a.nearest:
+        return nearest_bench(a)
     if a.tick:
         return tick(a)
     dev = torch.device("cuda:0")
@@ -78,8 +140,9 @@ def main(argv=None):
 
 
 def tick(a):
-    """Path-following tick: discretize + run (two launches) vs run_path (one launch), same robots and state.
-    Each variant runs its own solver handle through `iters` warm-started ticks on fixed measurements."""
+    """Path-following tick: discretize + run (two launches) vs run_path (one launch) vs follow_path (nearest point +
+    run_path + path-error check), same robots and state. Each variant runs its own solver handle through `iters`
+    warm-started ticks on fixed measurements; follow_path feeds its path_u back (0 at the first tick)."""
     from nmpc_nav_control_amd.batch import BatchSolver
     from nmpc_nav_control_amd.path import discretize as disc
     dev = torch.device("cuda:0")
@@ -88,10 +151,13 @@ def tick(a):
     S, NS, U = (torch.from_numpy(x).to(dev) for x in (segs, nseg, nu))
     traj = torch.empty((N + 1, 3, B), dtype=torch.float32, device=dev)
     disc(S, NS, U, 1 / 40, N + 1, traj=traj)
-    pose = traj[0].clone()
+    pose = torch.from_numpy(seeded_poses(segs, nseg, nu)).to(dev)
     vel = torch.zeros(3, B, device=dev)
+    path_u = torch.zeros(B, dtype=torch.float64, device=dev)
+    err = torch.empty((2, B), dtype=torch.float64, device=dev)
+    off = torch.empty(B, dtype=torch.uint8, device=dev)
     res = {}
-    for name in ("two_launch", "one_launch"):
+    for name in ("two_launch", "one_launch", "follow_path"):
         s = BatchSolver("diff", N, B, device=dev)
         u0 = torch.zeros(2, B, device=dev)
         st = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -100,8 +166,11 @@ def tick(a):
             if name == "two_launch":
                 disc(S, NS, U, 1 / 40, N + 1, traj=traj)
                 s.run(pose, vel, traj, u0=u0, status=st)
-            else:
+            elif name == "one_launch":
                 s.run_path(pose, vel, S, NS, U, 1 / 40, traj_out=None, u0=u0, status=st)
+            else:
+                s.follow_path(pose, vel, S, NS, path_u, 1 / 40, max_pos_err=1.0, max_ori_err=math.pi, err=err,
+                              off_path=off, u0=u0, status=st)
         for _ in range(5):
             step()
         torch.cuda.synchronize()
