@@ -165,12 +165,96 @@ int nmpc_batch_run_path(nmpc_batch* b, int B, const float* pose, const float* ve
  * Everything else as nmpc_batch_run_path. One departure from the node: it skips the solve of an off-path robot
  * (:663); here that robot's solve still runs (its iterate and carried refs advance) and only its command is
  * stopped. The node then waits for a new goal, which resets the controller anyway: pass reset[i] = 1 with it.
+ * (nmpc_batch_node_tick below does skip that solve.)
  * sample_period must be finite here. */
 int nmpc_batch_follow_path(nmpc_batch* b, int B, const float* pose, const float* vel, const float* steer,
                            const nmpc_path_segment* segs, int seg_stride, const int* nseg, double* path_u,
                            double sample_period, int is_holonomic, double max_pos_err, double max_ori_err,
                            const unsigned char* reset, double* err, unsigned char* off_path, float* traj_out,
                            float* cmd, float* u0, int* status, int* qp_iter, float* qp_res, void* stream);
+
+/* The node's control cycle (NMPCNavControlROS::mainCycle, NMPCNavControlROS.cpp:516-538) for B robots, each in its
+ * own state, in one call: the gate (two small launches) decides per robot what the node would do this tick, the robots that
+ * solve are compacted on the device, and the solve launch works for them alone. No host synchronisation; everything is
+ * queued on `stream`. */
+#define NMPC_NODE_IDLE 0
+#define NMPC_NODE_GOTO_POSE 1
+#define NMPC_NODE_FOLLOW_PATH 2
+#define NMPC_NODE_BREAK 3
+#define NMPC_NODE_ERROR 4
+
+#define NMPC_NODE_EV_NONE 0          /* Idle / Error: the node publishes nothing */
+#define NMPC_NODE_EV_SOLVED 1        /* executeNMPC ran and succeeded: cmd is the command */
+#define NMPC_NODE_EV_ARRIVED 2       /* end of trajectory (:636-643, :681-694): stop command, -> Idle */
+#define NMPC_NODE_EV_GOAL_TOO_FAR 3  /* :622-627: stop command, -> Idle */
+#define NMPC_NODE_EV_OFF_PATH 4      /* :658-664: stop command, -> Error */
+#define NMPC_NODE_EV_SOLVE_FAILED 5  /* status != 0 (:716-719): zero cmd, -> Error */
+#define NMPC_NODE_EV_BREAK 6         /* processBreak :612-616: stop command, -> Idle */
+
+typedef struct nmpc_node_params {
+    double final_pos_err, final_ori_err; /* m, rad: final_position_error / final_orientation_error
+                                          * (nmpc_nav_control.yaml:7-8; the yaml is in degrees) */
+    double max_goal_dist;                /* m: max_goal_pose_dist (:11) */
+    double max_pos_err, max_ori_err;     /* m, rad: max_pos_error_to_path / max_ori_error_to_path (:12-13) */
+    int enable_safe_conditions;          /* :10; 0 switches the goal-distance and the path-error guard off */
+    /* 1 (default): the end-of-trajectory test compares the signed ang = normAngRad(pose.theta - ref.theta) with
+     * final_ori_err, exactly as NMPCNavControlROS.cpp:638-639 / :683-684 write it (so any negative heading error
+     * counts as arrived); 0: |ang|. */
+    int final_ori_signed;
+    double sample_period; /* PathDiscretizer arguments, as nmpc_batch_run_path (the node: getDeltaTime(), false) */
+    int is_holonomic;
+} nmpc_node_params;
+/* The shipped nmpc_nav_control.yaml (0.01 m, 1 deg, 2 m, 0.5 m, 60 deg, safe conditions on), degrees converted to
+ * radians; final_ori_signed 1, sample_period 1/40 s (the codegen yaml's dt), is_holonomic 0. */
+int nmpc_node_params_default(nmpc_node_params* np);
+
+/* One tick of the node for robots [0, B). Arrays are device pointers, [field][B]:
+ *   mode     [B] in/out NMPC_NODE_*; a value above 4 is read as Error (and written back as NMPC_NODE_ERROR)
+ *   pose, vel, steer  as nmpc_batch_run
+ *   goal     [3][B] {x, y, theta}, read for GOTO_POSE robots; NULL when no robot is in GOTO_POSE
+ *   segs, seg_stride, nseg, path_u  as nmpc_batch_follow_path, read / written for FOLLOW_PATH robots only; segs,
+ *            nseg and path_u may all be NULL when no robot is in FOLLOW_PATH. A robot's list is its active path
+ *   reset    [B] in/out or NULL: pending controller reset. The node's goal and path callbacks call reset_mpc() at
+ *            once (:304-327), which shows only at the next solve: reset[i] is consumed (and cleared to 0) when
+ *            robot i solves and stays set while it does not
+ *   event    [B] out NMPC_NODE_EV_* or NULL
+ *   err      [2][B] out or NULL: path errors of the FOLLOW_PATH robots that reached the nearest-point step, NaN
+ *            elsewhere
+ *   traj_out [N+1][3][B] out or NULL: the reference poses each solving robot used; NaN for the others
+ *   n_solved device int[1] out or NULL: robots that ran a solve
+ *   cmd, u0, status, qp_iter, qp_res  as nmpc_batch_run; all zero for a robot that did not solve
+ * A robot in a mode whose inputs are NULL goes to Error with EV_NONE. Per robot (all tests in fp64 on the fp32
+ * inputs widened exactly; dist and normAngRad as utils.h):
+ *   IDLE, ERROR   nothing runs: event NONE, the mode stays.
+ *   BREAK         stop command, -> Idle, event BREAK.
+ *   GOTO_POSE     d = dist(goal, pose). enable_safe_conditions && d >= max_goal_dist: stop, -> Idle, GOAL_TOO_FAR.
+ *                 Else d <= final_pos_err && ang <= final_ori_err: stop, -> Idle, ARRIVED. Else solve on the
+ *                 one-pose reference (traj_len 1, padded with the goal: diff's terminal-weight hack fires, as in
+ *                 the node).
+ *   FOLLOW_PATH   nseg < 1: -> Idle, EV_NONE (executeNMPC's empty list, :702-705). Else the nearest point from
+ *                 path_u[i] and the path errors (exactly nmpc_path_nearest / nmpc_batch_follow_path, the
+ *                 holonomic heading for omni4); path_u[i] is updated. enable_safe_conditions and an error >= its
+ *                 threshold (+inf or NaN: that comparison is off): stop, -> Error, OFF_PATH, and the robot does
+ *                 NOT solve. Else getNextNPoses (N+1 poses, bit-identical to nmpc_path_discretize), then the end
+ *                 test against the last pose (in fp64, before its rounding to fp32): stop, -> Idle, ARRIVED, or
+ *                 the solve on those poses.
+ *   A solve with status != 0: zero cmd, -> Error, SOLVE_FAILED; the robot keeps its iterate and carried refs
+ *   (nmpc_batch_run's rule).
+ * A robot that does not solve is not touched: its rows of the iterate and the carried refs, its warm flag, its
+ * scratch records and its placement key are bit for bit what they were. The solve is nmpc_batch_run's on the gate's
+ * references: the kernel form follows B (nmpc_batch_plan_ex, NMPC_PLAN_RUN), the grid is sized for B, and blocks
+ * past the active count leave at once. Placement: the active robots fill the lowest team slots, in index order
+ * under NMPC_SCHED_OFF (and AUTO below the dense threshold, and in the one-robot-per-block forms), hardest first
+ * under SORTED (and AUTO when dense); INTERLEAVED and SPREAD fall back to SORTED for node ticks.
+ * sample_period must be finite and >= 0.
+ * Out of scope (the caller's, on the host): the upcoming_path_ queue, the velocity-sign split of
+ * processPathBuffers (:576-595) and the hop to the next queued path at :686-690 -- on ARRIVED the caller hands the
+ * robot its next part and sets reset[i]; and getInputData (the TF lookups and the finite-difference velocity). */
+int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsigned char* mode, const float* pose,
+                         const float* vel, const float* steer, const float* goal, const nmpc_path_segment* segs,
+                         int seg_stride, const int* nseg, double* path_u, unsigned char* reset, unsigned char* event,
+                         double* err, float* traj_out, int* n_solved, float* cmd, float* u0, int* status,
+                         int* qp_iter, float* qp_res, void* stream);
 
 /* Kernel variant: NMPC_KERNEL_TEAM (16-lane team per robot, DPP row exchange) is the only one; any other value
  * returns NMPC_ERR_UNSUPPORTED. (The round-1 one-lane-per-robot kernel was removed: its fp32 factor is not

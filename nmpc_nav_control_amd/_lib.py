@@ -56,6 +56,20 @@ class LaunchPlan(ctypes.Structure):
                 ("record_layout", ctypes.c_int), ("warm_tag", ctypes.c_int), ("record_bytes", ctypes.c_size_t)]
 
 
+class NodeParamsStruct(ctypes.Structure):
+    """Mirror of nmpc_node_params (include/nmpc_amd/nmpc_batch.h)."""
+    _fields_ = [("final_pos_err", ctypes.c_double), ("final_ori_err", ctypes.c_double),
+                ("max_goal_dist", ctypes.c_double), ("max_pos_err", ctypes.c_double), ("max_ori_err", ctypes.c_double),
+                ("enable_safe_conditions", ctypes.c_int), ("final_ori_signed", ctypes.c_int),
+                ("sample_period", ctypes.c_double), ("is_holonomic", ctypes.c_int)]
+
+
+# NMPC_NODE_* (a robot's state in the node's state machine) and NMPC_NODE_EV_* (what the tick did for it)
+NODE_IDLE, NODE_GOTO_POSE, NODE_FOLLOW_PATH, NODE_BREAK, NODE_ERROR = 0, 1, 2, 3, 4
+(NODE_EV_NONE, NODE_EV_SOLVED, NODE_EV_ARRIVED, NODE_EV_GOAL_TOO_FAR, NODE_EV_OFF_PATH, NODE_EV_SOLVE_FAILED,
+ NODE_EV_BREAK) = range(7)
+
+
 class CodegenDesc(ctypes.Structure):
     """Mirror of nmpc_codegen_desc (include/nmpc_amd/nmpc_capsule.h)."""
     _fields_ = [("model", ctypes.c_int), ("N", ctypes.c_int), ("tf", ctypes.c_double),
@@ -81,7 +95,7 @@ class SolverCapsule(ctypes.Structure):
 BATCH_SYMBOLS = [
     "nmpc_model_dims", "nmpc_model_params_default", "nmpc_model_params_set_limits", "nmpc_batch_create",
     "nmpc_batch_destroy", "nmpc_batch_set_params", "nmpc_batch_get_params", "nmpc_batch_init_iterate",
-    "nmpc_batch_solve", "nmpc_batch_solve_iterate", "nmpc_batch_run", "nmpc_batch_run_path", "nmpc_batch_follow_path", "nmpc_batch_state", "nmpc_batch_warm_state", "nmpc_batch_warm_rule", "nmpc_batch_plan", "nmpc_batch_plan_ex", "nmpc_batch_set_record_layout", "nmpc_batch_forget_warm", "nmpc_batch_set_kernel", "nmpc_batch_set_schedule",
+    "nmpc_batch_solve", "nmpc_batch_solve_iterate", "nmpc_batch_run", "nmpc_batch_run_path", "nmpc_batch_follow_path", "nmpc_batch_node_tick", "nmpc_node_params_default", "nmpc_batch_state", "nmpc_batch_warm_state", "nmpc_batch_warm_rule", "nmpc_batch_plan", "nmpc_batch_plan_ex", "nmpc_batch_set_record_layout", "nmpc_batch_forget_warm", "nmpc_batch_set_kernel", "nmpc_batch_set_schedule",
     "nmpc_fleet_sim_step", "nmpc_fleet_sim_step_renew", "nmpc_fleet_hash",
     "nmpc_last_error", "nmpc_version", "nmpc_path_discretize", "nmpc_path_nearest", "nmpc_codegen_default", "nmpc_capsule_new",
     "nmpc_capsule_delete", "nmpc_capsule_create", "nmpc_capsule_reset", "nmpc_capsule_update_params",
@@ -134,6 +148,9 @@ def lib():
     d = ctypes.c_double
     L.nmpc_batch_follow_path.argtypes = [vp, i, vp, vp, vp, vp, i, vp, vp, d, i, d, d, vp, vp, vp, vp, vp, vp, vp, vp,
                                          vp, vp]
+    L.nmpc_node_params_default.argtypes = [ctypes.POINTER(NodeParamsStruct)]
+    L.nmpc_batch_node_tick.argtypes = [vp, i, ctypes.POINTER(NodeParamsStruct), vp, vp, vp, vp, vp, vp, i, vp, vp, vp,
+                                       vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.nmpc_batch_set_kernel.argtypes = [vp, i]
     L.nmpc_batch_set_schedule.argtypes = [vp, i]
     L.nmpc_batch_state.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), c_int_p]

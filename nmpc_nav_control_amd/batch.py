@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from ._lib import (KERNELS, MODEL_IDS, PLAN_MODES, REC_LAYOUTS, SCHEDULES, FleetRenew, FleetStats, LaunchPlan,
-                   ModelParams, check, default_params, lib, model_dims)
+                   ModelParams, NodeParamsStruct, check, default_params, lib, model_dims)
 
 
 def _ptr(t, dtype=None, shape=None, name="argument"):
@@ -34,6 +34,28 @@ F32, I32, I64, U8 = torch.float32, torch.int32, torch.int64, (torch.uint8, torch
 def _stream(stream):
     s = stream if stream is not None else torch.cuda.current_stream()
     return ctypes.c_void_p(s.cuda_stream)
+
+
+class NodeParams:
+    """nmpc_node_params (include/nmpc_amd/nmpc_batch.h): the node's thresholds, angles in radians. ``default()``
+    is the shipped nmpc_nav_control.yaml; keyword arguments override fields (``NodeParams.default(max_pos_err=1.0)``)."""
+
+    def __init__(self, **fields):
+        self.c = NodeParamsStruct()
+        check(lib().nmpc_node_params_default(ctypes.byref(self.c)), "nmpc_node_params_default")
+        for k, v in fields.items():
+            if k not in dict(NodeParamsStruct._fields_):
+                raise AttributeError(f"nmpc_node_params has no field {k}")
+            setattr(self.c, k, v)
+
+    @classmethod
+    def default(cls, **fields):
+        return cls(**fields)
+
+    def __getattr__(self, k):
+        if k != "c" and k in dict(NodeParamsStruct._fields_):
+            return getattr(self.c, k)
+        raise AttributeError(k)
 
 
 class BatchSolver:
@@ -251,6 +273,35 @@ class BatchSolver:
             _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)),
             "nmpc_batch_follow_path")
 
+    def node_tick(self, node_params, mode, pose, vel, goal=None, segs=None, nseg=None, path_u=None, steer=None,
+                  reset=None, event=None, err=None, traj_out=None, n_solved=None, cmd=None, u0=None, status=None,
+                  qp_iter=None, qp_res=None, stream=None):
+        """One tick of the node's state machine for B robots, each in its own state (nmpc_batch_node_tick): mode
+        uint8 [B] in/out (NODE_*), goal float32 [3][B] for the GOTO_POSE robots, segs / nseg / path_u as follow_path
+        for the FOLLOW_PATH ones (each group may be None when no robot is in that mode), reset uint8 [B] in/out the
+        pending controller resets (consumed by the robots that solve). event uint8 [B] receives NODE_EV_*, err
+        float64 [2][B] the path errors (NaN for the others), traj_out the references of the solving robots (NaN for
+        the others), n_solved int32 [1] their count. Robots that do not solve keep their resident state bit for bit
+        and get zero outputs. node_params: a NodeParams."""
+        B = pose.shape[1]
+        if not 0 <= B <= self.capacity:
+            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        stride = 1
+        if segs is not None:
+            if segs.dim() != 3 or segs.shape[0] != B or segs.shape[2] != 16:
+                raise ValueError(f"segs: expected shape ({B}, S, 16), got {tuple(segs.shape)}")
+            stride = segs.shape[1]
+        check(lib().nmpc_batch_node_tick(
+            self._h, B, ctypes.byref(node_params.c), _ptr(mode, torch.uint8, (B,), "mode"),
+            _ptr(pose, F32, (3, B), "pose"), _ptr(vel, F32, (3, B), "vel"), _ptr(steer, F32, (B,), "steer"),
+            _ptr(goal, F32, (3, B), "goal"), _ptr(segs, torch.float64, None, "segs"), stride,
+            _ptr(nseg, I32, (B,), "nseg"), _ptr(path_u, torch.float64, (B,), "path_u"),
+            _ptr(reset, torch.uint8, (B,), "reset"), _ptr(event, torch.uint8, (B,), "event"),
+            _ptr(err, torch.float64, (2, B), "err"), _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"),
+            _ptr(n_solved, I32, (1,), "n_solved"), _ptr(cmd, F32, (3, B), "cmd"), _ptr(u0, F32, (self.nu, B), "u0"),
+            _ptr(status, I32, (B,), "status"), _ptr(qp_iter, I32, (B,), "qp_iter"),
+            _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)), "nmpc_batch_node_tick")
+
     def fleet_sim_step(self, path, s, pose, vel, steer, u0, status, traj, traj_len, advance=True, stream=None):
         B = pose.shape[1]
         if not 0 <= B <= self.capacity:
@@ -336,4 +387,4 @@ def _hip():
     return _hip_lib
 
 
-__all__ = ["BatchSolver", "ModelParams", "default_params"]
+__all__ = ["BatchSolver", "ModelParams", "NodeParams", "default_params"]

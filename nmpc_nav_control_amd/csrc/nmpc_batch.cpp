@@ -51,6 +51,14 @@ struct nmpc_batch {
     int rec_split = 0;
     double* path_err = nullptr;  // [2][capacity] path errors of nmpc_batch_follow_path when the caller keeps none
                                  // (allocated at the first such call)
+    // node ticks (nmpc_batch_node_tick), allocated at the first one: the gate's reference poses [N+1][3][capacity]
+    // and their lengths, the robots that solve (active [capacity], their count node_n [1]) and a status array for
+    // callers that keep none
+    float* node_traj = nullptr;
+    int* node_len = nullptr;
+    unsigned char* node_active = nullptr;
+    int* node_n = nullptr;
+    int* node_status = nullptr;
 #ifdef NMPC_HYBRID
     // hybrid launch (A/B build only, -DNMPC_HYBRID, NMPC_AMD_HYBRID=H): in a team-kernel launch the robots whose last
     // IPM count was >= H (at most hybrid_cap of them, the hardest first) run the segmented row-parallel kernel (one
@@ -250,10 +258,20 @@ hipError_t schedule(nmpc_batch* b, KArgs& a, int mode, hipStream_t s)
     // the row-parallel kernel keeps the wide single-direction records; the team kernel the handle's layout
     a.rec_split = (!a.rowpar && b->kp.ipm == NMPC_IPM_SINGLE) ? b->rec_split : 0;
     a.warm_tag = warm_tag_of(b, a);
-    if (a.rowpar) return hipSuccess;  // one robot per wave: nothing to place
+    if (a.rowpar && !a.n_active) return hipSuccess;  // one robot per wave: nothing to place
     a.dense = ((a.B + 3) / 4 > b->n_simd) ? 1 : 0;  // 4 teams per wave
     // small batches leave most of the chip idle: one wave per robot, whose spare rows integrate P0's stages
     a.split = (!a.dense && a.B <= b->split_max) ? 1 : 0;
+    if (a.n_active) {
+        // node tick: every form takes the compacted order (the robots that solve first). The forms with one robot
+        // per block keep index order; the team kernel follows the handle's schedule (interleaved and spread: sorted)
+        int layout = b->sched;
+        if (layout == NMPC_SCHED_AUTO) layout = a.dense ? NMPC_SCHED_SORTED : NMPC_SCHED_OFF;
+        if (a.rowpar) a.dense = a.split = 0;
+        const int sorted = (!a.rowpar && !a.split && layout != NMPC_SCHED_OFF) ? 1 : 0;
+        a.order = b->order;
+        return launch_node_order(b->iter_key, b->node_active, a.B, sorted, b->order, b->node_n, s);
+    }
     if (a.split) return hipSuccess;  // one robot per wave: nothing to place
 #ifdef NMPC_HYBRID
     // (the hybrid launch mixes the kernels in one tick: only where they share the record layout)
@@ -353,6 +371,21 @@ __global__ void k_path_guard(int B, const double* err, double max_pos, double ma
     if (off_path) off_path[i] = off ? 1 : 0;
     if (off && cmd)
         for (int j = 0; j < 3; j++) cmd[(size_t)j * B + i] = 0.0f;
+}
+
+// after a node tick's solve launch: a robot that solved has consumed its pending reset, and a failed solve sends it
+// to Error (NMPCNavControlROS.cpp:716-719); n_solved receives the active count
+__global__ void k_node_finish(int B, const unsigned char* active, const int* status, const int* n_active,
+                              unsigned char* mode, unsigned char* event, unsigned char* reset, int* n_solved)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && n_solved) n_solved[0] = n_active[0];
+    if (i >= B || !active[i]) return;
+    if (reset) reset[i] = 0;
+    if (status[i] != 0) {
+        mode[i] = NMPC_NODE_ERROR;
+        if (event) event[i] = NMPC_NODE_EV_SOLVE_FAILED;
+    }
 }
 
 int check_params(const nmpc_model_params* prm)
@@ -573,6 +606,11 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->sorted);
     (void)hipFree(b->warm);
     (void)hipFree(b->path_err);
+    (void)hipFree(b->node_traj);
+    (void)hipFree(b->node_len);
+    (void)hipFree(b->node_active);
+    (void)hipFree(b->node_n);
+    (void)hipFree(b->node_status);
 #ifdef NMPC_HYBRID
     (void)hipFree(b->hyb_n);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
@@ -823,6 +861,112 @@ int nmpc_batch_follow_path(nmpc_batch* b, int B, const float* pose, const float*
     hipLaunchKernelGGL(k_path_guard, dim3((B + 255) / 256), dim3(256), 0, s, B, err, max_pos_err, max_ori_err, use_pos,
                        use_ori, off_path, cmd);
     return hip_err(hipGetLastError(), "path_guard launch");
+}
+
+int nmpc_node_params_default(nmpc_node_params* np)
+{
+    if (!np) return set_err(NMPC_ERR_ARG, "node params is NULL");
+    std::memset(np, 0, sizeof(*np));
+    const double deg = M_PI / 180.0;
+    np->final_pos_err = 0.01;        // nmpc_nav_control.yaml:7
+    np->final_ori_err = 1.0 * deg;   // :8
+    np->enable_safe_conditions = 1;  // :10
+    np->max_goal_dist = 2.0;         // :11
+    np->max_pos_err = 0.5;           // :12
+    np->max_ori_err = 60.0 * deg;    // :13
+    np->final_ori_signed = 1;        // NMPCNavControlROS.cpp:638-639 compares the signed angle
+    np->sample_period = 1.0 / 40.0;  // getDeltaTime(): nmpc_nav_control_acados_models.yaml:28
+    np->is_holonomic = 0;            // NMPCNavControlROS.cpp:666
+    return NMPC_OK;
+}
+
+int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsigned char* mode, const float* pose,
+                         const float* vel, const float* steer, const float* goal, const nmpc_path_segment* segs,
+                         int seg_stride, const int* nseg, double* path_u, unsigned char* reset, unsigned char* event,
+                         double* err, float* traj_out, int* n_solved, float* cmd, float* u0, int* status,
+                         int* qp_iter, float* qp_res, void* stream)
+{
+    const TraceRange trace("nmpc_batch_node_tick");
+    // the checks that need no handle come first
+    if (!np) return set_err(NMPC_ERR_ARG, "node params is NULL");
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!mode) return set_err(NMPC_ERR_ARG, "mode is required");
+    if (segs && seg_stride < 1) return set_err(NMPC_ERR_ARG, "seg_stride < 1");
+    if (!std::isfinite(np->sample_period) || np->sample_period < 0.0)
+        return set_err(NMPC_ERR_ARG, "sample_period must be finite and >= 0");
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (B == 0) return NMPC_OK;
+    if (!pose || !vel) return set_err(NMPC_ERR_ARG, "pose and vel are required");
+    const bool paths = segs && nseg && path_u;
+    if (paths && node_gate_lds_bytes(b->prm.N) > 65536)
+        return set_err(NMPC_ERR_UNSUPPORTED, "horizon too long for the gate's path march");
+    hipStream_t s = (hipStream_t)stream;
+    if (!b->node_traj) {
+        const size_t S = (size_t)b->capacity;
+        hipError_t e;
+        if ((e = hipMalloc(&b->node_len, sizeof(int) * S)) != hipSuccess ||
+            (e = hipMalloc(&b->node_active, S)) != hipSuccess ||
+            (e = hipMalloc(&b->node_n, sizeof(int))) != hipSuccess ||
+            (e = hipMalloc(&b->node_status, sizeof(int) * S)) != hipSuccess ||
+            (e = hipMalloc(&b->node_traj, sizeof(float) * 3 * (size_t)(b->prm.N + 1) * S)) != hipSuccess)
+            return hip_err(e, "hipMalloc");
+    }
+    if (!status) status = b->node_status;  // (the finish launch reads it)
+    NodeGateArgs g;
+    std::memset(&g, 0, sizeof(g));
+    g.B = B;
+    g.N = b->prm.N;
+    g.nu = b->nu;
+    g.seg_stride = paths ? seg_stride : 1;
+    g.holo_err = b->prm.model == NMPC_MODEL_OMNI4AMR ? 1 : 0;  // NMPCNavControlROS.cpp:654
+    g.np = *np;
+    g.mode = mode;
+    g.pose = pose;
+    g.goal = goal;
+    g.segs = paths ? segs : nullptr;
+    g.nseg = paths ? nseg : nullptr;
+    g.path_u = paths ? path_u : nullptr;
+    g.event = event;
+    g.err = err;
+    g.traj = b->node_traj;
+    g.traj_len = b->node_len;
+    g.active = b->node_active;
+    g.traj_out = traj_out;
+    g.cmd = cmd;
+    g.u0 = u0;
+    g.qp_res = qp_res;
+    g.status = status;
+    g.qp_iter = qp_iter;
+    int rc = hip_err(launch_node_gate(g, s), "node_gate launch");
+    if (rc) return rc;
+    // nmpc_batch_run's launch on the gate's references, for the compacted robots
+    KArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.stride = b->capacity;
+    a.sstride = b->capacity;
+    a.xbar = b->xbar;
+    a.ubar = b->ubar;
+    a.carried = b->carried;
+    a.scratch = b->scratch;
+    a.pose = pose;
+    a.vel = vel;
+    a.steer = steer;
+    a.traj = b->node_traj;
+    a.traj_len = b->node_len;
+    a.reset = reset;
+    a.cmd = cmd;
+    a.u0 = u0;
+    a.status = status;
+    a.qp_iter = qp_iter;
+    a.qp_res = qp_res;
+    a.n_active = b->node_n;
+    rc = hip_err(launch(b, a, kModeRun, s), "node_tick solve launch");
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_node_finish, dim3((B + 255) / 256), dim3(256), 0, s, B, b->node_active, status, b->node_n,
+                       mode, event, reset, n_solved);
+    return hip_err(hipGetLastError(), "node_finish launch");
 }
 
 int nmpc_batch_set_kernel(nmpc_batch* b, int kernel)

@@ -69,6 +69,9 @@ struct KArgs {
     float* utraj;  // [N*NU][B]
     // team placement (schedule.hip): team slot -> instance, or nullptr (slot i = instance i)
     const int* order;
+    // node ticks (nmpc_batch_node_tick): device count of the robots that solve, the first *n_active slots of `order`;
+    // a team / block whose slot is past it leaves at once. nullptr: every slot below B runs
+    const int* n_active;
     int* iter_key;  // [stride] resident: executed IPM iterations of the last solve, or nullptr
     unsigned char* warm;  // [stride] resident: the robot's last solve succeeded and its records hold its multipliers
                           // in the layout tagged (NMPC_WARM_TAG_*), 0 otherwise; nullptr: cold start, nothing written
@@ -111,6 +114,10 @@ hipError_t launch_fleet_sim(const KParams& P, int B, int stride, float* path, fl
                             float* steer, const float* u0, const int* status, const float* carried, float* traj,
                             int* traj_len, int advance, const nmpc_fleet_renew* renew, hipStream_t stream);
 hipError_t launch_team_order(const int* key, int B, int layout, int* sorted, int* order, hipStream_t stream);
+// node ticks: the robots with active[i] != 0 first (hardest first by key when `sorted`, else in index order), the
+// others behind them; n_active[0] = their count
+hipError_t launch_node_order(const int* key, const unsigned char* active, int B, int sorted, int* order, int* n_active,
+                             hipStream_t stream);
 #ifdef NMPC_HYBRID
 // sorted order (hardest first) plus nhard[0] = min(#robots with key >= H, cap): the hybrid launch's split
 hipError_t launch_hybrid_order(const int* key, int B, int H, int cap, int* order, int* nhard, hipStream_t stream);
@@ -123,5 +130,29 @@ hipError_t launch_path_discretize(int B, const nmpc_path_segment* segs, int seg_
 hipError_t launch_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
                                const float* pose, const double* lo, const double* hi, int holo, double* nearest_u,
                                double* near, double* err, hipStream_t stream);
+
+// The gate of a node tick (node_gate.hip): per robot the mode switch of NMPCNavControlROS::mainCycle up to the solve
+// decision. Device pointers, [field][B]; the nullable ones as in nmpc_batch_node_tick.
+struct NodeGateArgs {
+    int B, N, nu, seg_stride;
+    int holo_err;  // heading of the path orientation error: 1 holonomic (omni4)
+    nmpc_node_params np;
+    unsigned char* mode;
+    const float* pose;
+    const float* goal;
+    const nmpc_path_segment* segs;
+    const int* nseg;
+    double* path_u;
+    unsigned char* event;
+    double* err;
+    float* traj;            // [N+1][3][B] handle-owned: the reference of every solving robot
+    int* traj_len;          // [B]
+    unsigned char* active;  // [B] 1: the robot solves this tick
+    float* traj_out;
+    float *cmd, *u0, *qp_res;
+    int *status, *qp_iter;
+};
+hipError_t launch_node_gate(const NodeGateArgs& g, hipStream_t stream);
+size_t node_gate_lds_bytes(int N);
 
 }  // namespace nmpc

@@ -102,7 +102,67 @@ __global__ __launch_bounds__(kOrderThreads) void k_team_order(const int* __restr
     }
 }
 
+// Node ticks (nmpc_batch_node_tick): the same stable counting sort with one more bin below every active one. The
+// robots with active[i] != 0 come first -- hardest first by key when `sorted`, in index order otherwise (one bin) --
+// and the others follow in index order; n_active[0] receives the count of the active ones, which is where the
+// inactive bin starts.
+constexpr int kNodeBins = kOrderBins + 1;
+
+__global__ __launch_bounds__(kOrderThreads) void k_node_order(const int* __restrict__ key,
+                                                               const unsigned char* __restrict__ active, int B,
+                                                               int sorted, int* __restrict__ order,
+                                                               int* __restrict__ n_active)
+{
+    __shared__ unsigned cnt[kNodeBins][kOrderThreads];
+    __shared__ unsigned part[kOrderThreads];
+    const int t = threadIdx.x;
+    const int E = (B + kOrderThreads - 1) / kOrderThreads;
+    const int i0 = min(B, t * E), i1 = min(B, i0 + E);
+    auto bin_of = [&](int i) -> int {
+        if (!active[i]) return kNodeBins - 1;
+        return sorted ? kOrderBins - 1 - min(max(key[i], 0), kOrderBins - 1) : 0;
+    };
+    for (int b = 0; b < kNodeBins; b++) cnt[b][t] = 0;
+    for (int i = i0; i < i1; i++) cnt[bin_of(i)][t]++;
+    __syncthreads();
+    // flattened index f = bin * T + thread; thread t scans f in [33 t, 33 t + 33)
+    unsigned loc[kNodeBins];
+    unsigned s = 0;
+#pragma unroll
+    for (int j = 0; j < kNodeBins; j++) {
+        const int f = t * kNodeBins + j;
+        loc[j] = s;
+        s += cnt[f / kOrderThreads][f % kOrderThreads];
+    }
+    part[t] = s;
+    __syncthreads();
+    for (int d = 1; d < kOrderThreads; d <<= 1) {
+        const unsigned v = (t >= d) ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    const unsigned base = part[t] - s;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kNodeBins; j++) {
+        const int f = t * kNodeBins + j;
+        cnt[f / kOrderThreads][f % kOrderThreads] = base + loc[j];
+    }
+    __syncthreads();
+    if (t == 0) n_active[0] = (int)cnt[kNodeBins - 1][0];  // (before thread 0's own scatter advances it)
+    for (int i = i0; i < i1; i++) order[cnt[bin_of(i)][t]++] = i;
+}
+
 }  // namespace
+
+hipError_t launch_node_order(const int* key, const unsigned char* active, int B, int sorted, int* order, int* n_active,
+                             hipStream_t stream)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_node_order, dim3(1), dim3(kOrderThreads), 0, stream, key, active, B, sorted, order, n_active);
+    return hipGetLastError();
+}
 
 hipError_t launch_team_order(const int* key, int B, int layout, int* sorted, int* order, hipStream_t stream)
 {

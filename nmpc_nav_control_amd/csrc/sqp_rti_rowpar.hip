@@ -207,10 +207,11 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
 #ifdef NMPC_HYBRID
     // hybrid launch (A/B build, role 2): block i takes the robot of rank i of the order, for the first hyb_n[0] ranks
     if (a.hyb_role == 2 && (int)blockIdx.x >= a.hyb_n[0]) return;
-    const int inst = (a.hyb_role == 2) ? a.order[blockIdx.x] : (int)blockIdx.x;
-#else
-    const int inst = (int)blockIdx.x;
 #endif
+    // node ticks: block s takes the robot of slot s of the order, for the first *n_active slots (the robots that
+    // solve); plain launches (order == nullptr): block i = robot i
+    if ((int)blockIdx.x >= a.B || (a.n_active && (int)blockIdx.x >= *a.n_active)) return;
+    const int inst = a.order ? __builtin_amdgcn_readfirstlane(a.order[blockIdx.x]) : (int)blockIdx.x;
     if (inst >= a.B) return;
     const int tid = (int)threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (an SGPR: branches on it are wave-uniform)

@@ -120,6 +120,8 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     constexpr int hoff = 0;
 #endif
     if (team >= a.B - hoff) return;  // whole DPP rows leave together
+    // node ticks: the robots that solve fill the first *n_active slots of the order; the other slots leave
+    if (a.n_active && team >= *a.n_active) return;
     const int N = P.N;
     const size_t S = (size_t)a.stride;  // resident state stride (capacity)
     const size_t Bn = (size_t)a.B;

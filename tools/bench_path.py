@@ -10,9 +10,15 @@ With --tick: a whole path-following tick of diff robots (N = num_poses - 1), the
 (nmpc_path_discretize + nmpc_batch_run) against the one-launch nmpc_batch_run_path and against
 nmpc_batch_follow_path (nearest point + run_path + path-error check), ms per tick each.
 
+With --node: nmpc_batch_node_tick on a mixed fleet of diff robots (N = num_poses - 1) at B = 4096 and 1024 with 100 %,
+50 % and 25 % of the robots active (half of them following a seeded path, half driving to a seeded goal 0.3-1 m
+away), the others Idle and scattered uniformly over the indices. In the same process, on the same references:
+nearest + discretize + run over the full B, and over a batch holding just the active robots. Three interleaved
+rounds of each, the median; one JSON line per (B, fraction).
+
 Poses of --nearest and --tick: the path points at the seeded nearest_u, displaced by a seeded offset of up to 0.1 m.
 
-usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick]
+usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick | --node]
 """
 import argparse
 import json
@@ -111,7 +117,10 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--tick", action="store_true")
     ap.add_argument("--nearest", action="store_true")
+    ap.add_argument("--node", action="store_true")
     a = ap.parse_args(argv)
+    if a.node:
+        return node_bench(a)
     if a.nearest:
         return nearest_bench(a)
     if a.tick:
@@ -183,6 +192,91 @@ def tick(a):
         res[name] = round(e0.elapsed_time(e1) / a.iters, 4)
         res[name + "_failed"] = int((st != 0).sum())
     print(json.dumps(dict(metric="path-following tick ms (diff N=%d, B=%d)" % (N, B), **res)), flush=True)
+
+
+def node_bench(a):
+    """node_tick against nearest + discretize + run (see the module docstring). Every handle runs warm-started ticks
+    on fixed measurements; path_u is fed back. `dropped` counts robots whose mode changed during the run (a failed
+    solve sends a robot to Error, which would shrink the active set)."""
+    from nmpc_nav_control_amd._lib import NODE_FOLLOW_PATH, NODE_GOTO_POSE
+    from nmpc_nav_control_amd.batch import BatchSolver, NodeParams
+    from nmpc_nav_control_amd.path import nearest
+    dev = torch.device("cuda:0")
+    N = a.num_poses - 1
+    npar = NodeParams.default()
+    stream = torch.cuda.current_stream()
+    i32, f64 = torch.int32, torch.float64
+    for B in (4096, 1024):
+        segs, nseg, nu = seeded_paths(B)
+        pose = seeded_poses(segs, nseg, nu)
+        rng = np.random.default_rng(B)
+        ang, r = rng.uniform(-math.pi, math.pi, B), rng.uniform(0.3, 1.0, B)
+        goal = np.stack([pose[0] + r * np.cos(ang), pose[1] + r * np.sin(ang),
+                         pose[2] + rng.uniform(0.2, 1.0, B)]).astype(np.float32)
+        perm = rng.permutation(B)
+        for frac in (1.0, 0.5, 0.25):
+            k = int(B * frac)
+            act = np.sort(perm[:k])
+            mode = np.zeros(B, np.uint8)
+            mode[act[0::2]] = NODE_FOLLOW_PATH
+            mode[act[1::2]] = NODE_GOTO_POSE
+            t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+
+            def fleet(idx):
+                """device inputs of the robots idx (a compact batch) and their outputs"""
+                n = len(idx)
+                d = dict(S=t(segs[idx]), NS=t(nseg[idx]), P=t(pose[:, idx]), V=torch.zeros(3, n, device=dev),
+                         G=t(goal[:, idx]), M=t(mode[idx]), U=torch.zeros(n, dtype=f64, device=dev),
+                         err=torch.empty((2, n), dtype=f64, device=dev), traj=torch.empty((N + 1, 3, n), device=dev),
+                         u0=torch.zeros(2, n, device=dev), st=torch.zeros(n, dtype=i32, device=dev),
+                         nan=torch.full((n,), math.nan, dtype=f64, device=dev))
+                d["solver"] = BatchSolver("diff", N, n, device=dev)
+                return d
+
+            node, full, small = fleet(np.arange(B)), fleet(np.arange(B)), fleet(act)
+            nsolved = torch.zeros(1, dtype=i32, device=dev)
+            tref = torch.empty((N + 1, 3, B), device=dev)
+
+            def node_step():
+                d = node
+                d["solver"].node_tick(npar, d["M"], d["P"], d["V"], goal=d["G"], segs=d["S"], nseg=d["NS"],
+                                      path_u=d["U"], err=d["err"], traj_out=tref, n_solved=nsolved, u0=d["u0"],
+                                      status=d["st"])
+
+            # the references of the parts: what the node tick solved on (the goal repeated, or the path poses)
+            node_step()
+            torch.cuda.synchronize()
+            node["solver"].init_iterate()
+            node["U"].zero_()
+            ref_full = torch.where(torch.isnan(tref), node["P"][None].expand(N + 1, 3, B), tref).contiguous()
+            len_full = torch.where(node["M"] == NODE_GOTO_POSE, 1, N + 1).to(i32)
+            ai = t(act)
+            ref_small, len_small = ref_full[:, :, ai].contiguous(), len_full[ai].contiguous()
+
+            def parts_step(d, ref, ln):
+                d["U"] = nearest(d["S"], d["NS"], d["P"], torch.stack([d["U"], d["nan"]]), err=d["err"])
+                discretize(d["S"], d["NS"], d["U"], 1 / 40, N + 1, traj=d["traj"])
+                d["solver"].run(d["P"], d["V"], ref, traj_len=ln, u0=d["u0"], status=d["st"])
+
+            ms = {"node_tick": [], "parts_full": [], "parts_active": []}
+            for _ in range(3):
+                ms["node_tick"].append(timed(node_step, a.iters, stream))
+                ms["parts_full"].append(timed(lambda: parts_step(full, ref_full, len_full), a.iters, stream))
+                ms["parts_active"].append(timed(lambda: parts_step(small, ref_small, len_small), a.iters, stream))
+            med = {k_: sorted(v)[1] for k_, v in ms.items()}
+            dropped = int((node["M"].cpu() != t(mode).cpu()).sum())
+            plan_b, plan_k = node["solver"].plan_ex(B, "run"), small["solver"].plan_ex(k, "run")
+            print(json.dumps(dict(
+                metric="node tick ms (diff N=%d)" % N, B=B, active=k, n_solved=int(nsolved.cpu()), dropped=dropped,
+                node_tick_ms=round(med["node_tick"], 4), parts_full_ms=round(med["parts_full"], 4),
+                parts_active_ms=round(med["parts_active"], 4),
+                node_over_parts_full=round(med["node_tick"] / med["parts_full"], 3),
+                node_over_parts_active=round(med["node_tick"] / med["parts_active"], 3),
+                rounds={k_: [round(x, 4) for x in v] for k_, v in ms.items()},
+                failed=dict(node=int((node["st"] != 0).sum()), full=int((full["st"] != 0).sum()),
+                            active=int((small["st"] != 0).sum())),
+                form_B="%s w%d" % (plan_b["kernel"], plan_b["waves_per_robot"]),
+                form_active="%s w%d" % (plan_k["kernel"], plan_k["waves_per_robot"]))), flush=True)
 
 
 if __name__ == "__main__":
