@@ -247,14 +247,75 @@ int nmpc_node_params_default(nmpc_node_params* np);
  * under NMPC_SCHED_OFF (and AUTO below the dense threshold, and in the one-robot-per-block forms), hardest first
  * under SORTED (and AUTO when dense); INTERLEAVED and SPREAD fall back to SORTED for node ticks.
  * sample_period must be finite and >= 0.
- * Out of scope (the caller's, on the host): the upcoming_path_ queue, the velocity-sign split of
- * processPathBuffers (:576-595) and the hop to the next queued path at :686-690 -- on ARRIVED the caller hands the
- * robot its next part and sets reset[i]; and getInputData (the TF lookups and the finite-difference velocity). */
+ * Out of scope here: the upcoming_path_ queue, the velocity-sign split of processPathBuffers (:576-595) and the hop
+ * to the next queued path at :686-690. A robot's list is one active path, and on ARRIVED the caller hands the robot
+ * its next part and sets reset[i]; nmpc_batch_node_tick_queue below keeps the whole path set on the device instead.
+ * Out of scope for both (the caller's, on the host): getInputData (the TF lookups and the finite-difference
+ * velocity). */
 int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsigned char* mode, const float* pose,
                          const float* vel, const float* steer, const float* goal, const nmpc_path_segment* segs,
                          int seg_stride, const int* nseg, double* path_u, unsigned char* reset, unsigned char* event,
                          double* err, float* traj_out, int* n_solved, float* cmd, float* u0, int* status,
                          int* qp_iter, float* qp_res, void* stream);
+
+/* The node tick with each robot's path-set queue on the device: the bookkeeping NMPCNavControlROS keeps in
+ * active_path_ / upcoming_path_ runs in the gate, so a mission of several parts (forward, reversing, forward again)
+ * needs no host round trip at the part ends. A robot's whole set stays in its records segs[i*seg_stride ..
+ * +npart[i]-1]; active_path_ is the parts [head, tail) and upcoming_path_ the parts [tail, npart). Same launches as
+ * nmpc_batch_node_tick (gate, march, order, solve, finish), no host synchronisation.
+ * (The value is parenthesised to keep this constant apart from the seven events of the plain tick above.) */
+/* end of a part with parts still queued (:686-692): stop command, stays FOLLOW_PATH */
+#define NMPC_NODE_EV_NEXT_PART (7)
+
+typedef struct nmpc_path_queue {
+    const int* npart;      /* [B] parts of robot i's whole set */
+    int* head;             /* [B] in/out: first active part */
+    int* tail;             /* [B] in/out: one past the last active part */
+    const int* frame;      /* [B][seg_stride] frame id per part as a number, or NULL: all equal (:589) */
+    const double* length;  /* [B][seg_stride] GetPathLength() per part, or NULL: part_length for every part */
+    double part_length;    /* default 1000: the node's SetPathLength(1000), :571 */
+    double max_active_len; /* default 5.0: max_active_path_length (nmpc_nav_control.yaml:6) */
+    double* remains;       /* [B] out or NULL: patch_remains (:374-375) for FOLLOW_PATH robots, NaN for the others */
+} nmpc_path_queue;
+int nmpc_path_queue_default(nmpc_path_queue* q); /* scalars as above, pointers NULL */
+
+/* Arguments: q, then those of nmpc_batch_node_tick without nseg. path_u[i] is active_path_u_, the path parameter
+ * relative to part head[i]. A new path set is given by writing the parts, npart[i], head[i] = tail[i] = 0,
+ * path_u[i] = 0, reset[i] = 1 (the path callbacks call reset_mpc(), :316 / :326) and mode[i] = FOLLOW_PATH.
+ * Dropping the parts with an empty frame id (:569) and decoding the messages stay with the caller. Everything not
+ * named here is nmpc_batch_node_tick's: the other modes, the outputs, the untouched non-solvers, placement, n_solved
+ * and the reset rule. Argument errors as there; also q NULL, npart / head / tail NULL while segs is given, and a
+ * non-finite part_length or max_active_len. Per FOLLOW_PATH robot, all in fp64:
+ *   1. nP = clamp(npart, 0, seg_stride), h = clamp(head, 0, nP), t = clamp(tail, h, nP): no segment outside the
+ *      robot's own records is read, and the clamped values are what is written back. nP < 1: -> Idle, EV_NONE, the
+ *      window untouched.
+ *   2. t == h (a new set): fill(0), processPathReceived's processPathBuffers(0.0) (:573). Still empty: -> Idle,
+ *      EV_NONE.
+ *   3. The nearest point over the parts [h, t) from path_u: nmpc_path_nearest's search on those parts, U.
+ *   4. The pop (:603-609): k = floor(U); if t - h > k: h += k, U -= k.
+ *   5. fill(U) (:652).
+ *   6. The path errors and the guard as in nmpc_batch_node_tick, with one difference: the pi of a part driven
+ *      backwards follows the FRONT part after the pop (active_path_.front().GetVelocity(), :655), where
+ *      nmpc_path_nearest takes the segment of nearest_u. The two differ only when U == t - h exactly (the end of the
+ *      window: nothing is popped, and the front part is the first one). OFF_PATH leaves head, tail and path_u as
+ *      updated so far, as the node does.
+ *   7. getNextNPoses over [h, t) from U, bit-identical to nmpc_path_discretize on those parts.
+ *   8. The end test on the last pose. Arrived with t == nP: -> Idle, ARRIVED. Arrived with parts queued: h += 1,
+ *      t += 1 (pop_front and push of the upcoming front without a sign or frame test, :687-689), path_u = 0, the mode
+ *      stays FOLLOW_PATH, EV_NEXT_PART, stop command; reset[i] is not touched. Else the robot solves.
+ *   9. remains[i] = r > 0 ? r - path_u : r with r = nP - h, from the values the tick leaves behind; NaN for a robot
+ *      that is not in FOLLOW_PATH after the tick (a failed solve included).
+ *   fill(U) is processPathBuffers (:576-595):
+ *      L = sum over k in [h, t) of len(k) * (k == h ? 1 - U : 1)
+ *      while L < max_active_len and t < nP:
+ *          if t > h: break if v[t-1] * v[t] < 0, or if frame is given and frame[t-1] != frame[t]
+ *          t += 1; L += len(t-1) */
+int nmpc_batch_node_tick_queue(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_queue* q,
+                               unsigned char* mode, const float* pose, const float* vel, const float* steer,
+                               const float* goal, const nmpc_path_segment* segs, int seg_stride, double* path_u,
+                               unsigned char* reset, unsigned char* event, double* err, float* traj_out,
+                               int* n_solved, float* cmd, float* u0, int* status, int* qp_iter, float* qp_res,
+                               void* stream);
 
 /* Kernel variant: NMPC_KERNEL_TEAM (16-lane team per robot, DPP row exchange) is the only one; any other value
  * returns NMPC_ERR_UNSUPPORTED. (The round-1 one-lane-per-robot kernel was removed: its fp32 factor is not

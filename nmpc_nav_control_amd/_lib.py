@@ -64,10 +64,18 @@ class NodeParamsStruct(ctypes.Structure):
                 ("sample_period", ctypes.c_double), ("is_holonomic", ctypes.c_int)]
 
 
+class PathQueueStruct(ctypes.Structure):
+    """Mirror of nmpc_path_queue (include/nmpc_amd/nmpc_batch.h)."""
+    _fields_ = [("npart", c_void_p), ("head", c_void_p), ("tail", c_void_p), ("frame", c_void_p),
+                ("length", c_void_p), ("part_length", ctypes.c_double), ("max_active_len", ctypes.c_double),
+                ("remains", c_void_p)]
+
+
 # NMPC_NODE_* (a robot's state in the node's state machine) and NMPC_NODE_EV_* (what the tick did for it)
 NODE_IDLE, NODE_GOTO_POSE, NODE_FOLLOW_PATH, NODE_BREAK, NODE_ERROR = 0, 1, 2, 3, 4
 (NODE_EV_NONE, NODE_EV_SOLVED, NODE_EV_ARRIVED, NODE_EV_GOAL_TOO_FAR, NODE_EV_OFF_PATH, NODE_EV_SOLVE_FAILED,
  NODE_EV_BREAK) = range(7)
+NODE_EV_NEXT_PART = 7  # nmpc_batch_node_tick_queue only
 
 
 class CodegenDesc(ctypes.Structure):
@@ -95,7 +103,8 @@ class SolverCapsule(ctypes.Structure):
 BATCH_SYMBOLS = [
     "nmpc_model_dims", "nmpc_model_params_default", "nmpc_model_params_set_limits", "nmpc_batch_create",
     "nmpc_batch_destroy", "nmpc_batch_set_params", "nmpc_batch_get_params", "nmpc_batch_init_iterate",
-    "nmpc_batch_solve", "nmpc_batch_solve_iterate", "nmpc_batch_run", "nmpc_batch_run_path", "nmpc_batch_follow_path", "nmpc_batch_node_tick", "nmpc_node_params_default", "nmpc_batch_state", "nmpc_batch_warm_state", "nmpc_batch_warm_rule", "nmpc_batch_plan", "nmpc_batch_plan_ex", "nmpc_batch_set_record_layout", "nmpc_batch_forget_warm", "nmpc_batch_set_kernel", "nmpc_batch_set_schedule",
+    "nmpc_batch_solve", "nmpc_batch_solve_iterate", "nmpc_batch_run", "nmpc_batch_run_path", "nmpc_batch_follow_path", "nmpc_batch_node_tick", "nmpc_node_params_default",
+    "nmpc_batch_node_tick_queue", "nmpc_path_queue_default", "nmpc_batch_state", "nmpc_batch_warm_state", "nmpc_batch_warm_rule", "nmpc_batch_plan", "nmpc_batch_plan_ex", "nmpc_batch_set_record_layout", "nmpc_batch_forget_warm", "nmpc_batch_set_kernel", "nmpc_batch_set_schedule",
     "nmpc_fleet_sim_step", "nmpc_fleet_sim_step_renew", "nmpc_fleet_hash",
     "nmpc_last_error", "nmpc_version", "nmpc_path_discretize", "nmpc_path_nearest", "nmpc_codegen_default", "nmpc_capsule_new",
     "nmpc_capsule_delete", "nmpc_capsule_create", "nmpc_capsule_reset", "nmpc_capsule_update_params",
@@ -151,6 +160,10 @@ def lib():
     L.nmpc_node_params_default.argtypes = [ctypes.POINTER(NodeParamsStruct)]
     L.nmpc_batch_node_tick.argtypes = [vp, i, ctypes.POINTER(NodeParamsStruct), vp, vp, vp, vp, vp, vp, i, vp, vp, vp,
                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.nmpc_path_queue_default.argtypes = [ctypes.POINTER(PathQueueStruct)]
+    L.nmpc_batch_node_tick_queue.argtypes = [vp, i, ctypes.POINTER(NodeParamsStruct), ctypes.POINTER(PathQueueStruct),
+                                             vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             vp]
     L.nmpc_batch_set_kernel.argtypes = [vp, i]
     L.nmpc_batch_set_schedule.argtypes = [vp, i]
     L.nmpc_batch_state.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), c_int_p]

@@ -302,6 +302,31 @@ class BatchSolver:
             _ptr(status, I32, (B,), "status"), _ptr(qp_iter, I32, (B,), "qp_iter"),
             _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)), "nmpc_batch_node_tick")
 
+    def node_tick_queue(self, node_params, queue, mode, pose, vel, goal=None, steer=None, reset=None, event=None,
+                        err=None, traj_out=None, n_solved=None, cmd=None, u0=None, status=None, qp_iter=None,
+                        qp_res=None, stream=None):
+        """node_tick with each robot's path-set queue on the device (nmpc_batch_node_tick_queue). queue: a
+        nmpc_nav_control_amd.path.PathQueue, which owns segs, npart, head, tail and path_u (and frame, length and
+        remains when it was built with them); the tick pops the parts behind each FOLLOW_PATH robot, extends its
+        active window, and at the end of a part hops to the next queued one (event NODE_EV_NEXT_PART). Everything
+        else as node_tick."""
+        B = pose.shape[1]
+        if not 0 <= B <= self.capacity:
+            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        if queue.B != B:
+            raise ValueError(f"queue: built for {queue.B} robots, the tick has {B}")
+        check(lib().nmpc_batch_node_tick_queue(
+            self._h, B, ctypes.byref(node_params.c), ctypes.byref(queue.struct()),
+            _ptr(mode, torch.uint8, (B,), "mode"), _ptr(pose, F32, (3, B), "pose"), _ptr(vel, F32, (3, B), "vel"),
+            _ptr(steer, F32, (B,), "steer"), _ptr(goal, F32, (3, B), "goal"),
+            _ptr(queue.segs, torch.float64, (B, queue.S, 16), "segs"), queue.S,
+            _ptr(queue.path_u, torch.float64, (B,), "path_u"), _ptr(reset, torch.uint8, (B,), "reset"),
+            _ptr(event, torch.uint8, (B,), "event"), _ptr(err, torch.float64, (2, B), "err"),
+            _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"), _ptr(n_solved, I32, (1,), "n_solved"),
+            _ptr(cmd, F32, (3, B), "cmd"), _ptr(u0, F32, (self.nu, B), "u0"), _ptr(status, I32, (B,), "status"),
+            _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)),
+            "nmpc_batch_node_tick_queue")
+
     def fleet_sim_step(self, path, s, pose, vel, steer, u0, status, traj, traj_len, advance=True, stream=None):
         B = pose.shape[1]
         if not 0 <= B <= self.capacity:

@@ -376,7 +376,8 @@ __global__ void k_path_guard(int B, const double* err, double max_pos, double ma
 // after a node tick's solve launch: a robot that solved has consumed its pending reset, and a failed solve sends it
 // to Error (NMPCNavControlROS.cpp:716-719); n_solved receives the active count
 __global__ void k_node_finish(int B, const unsigned char* active, const int* status, const int* n_active,
-                              unsigned char* mode, unsigned char* event, unsigned char* reset, int* n_solved)
+                              unsigned char* mode, unsigned char* event, unsigned char* reset, int* n_solved,
+                              double* remains)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0 && n_solved) n_solved[0] = n_active[0];
@@ -385,6 +386,7 @@ __global__ void k_node_finish(int B, const unsigned char* active, const int* sta
     if (status[i] != 0) {
         mode[i] = NMPC_NODE_ERROR;
         if (event) event[i] = NMPC_NODE_EV_SOLVE_FAILED;
+        if (remains) remains[i] = __builtin_nan("");  // (node_tick_queue: no longer in FollowPath)
     }
 }
 
@@ -880,15 +882,32 @@ int nmpc_node_params_default(nmpc_node_params* np)
     return NMPC_OK;
 }
 
-int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsigned char* mode, const float* pose,
-                         const float* vel, const float* steer, const float* goal, const nmpc_path_segment* segs,
-                         int seg_stride, const int* nseg, double* path_u, unsigned char* reset, unsigned char* event,
-                         double* err, float* traj_out, int* n_solved, float* cmd, float* u0, int* status,
-                         int* qp_iter, float* qp_res, void* stream)
+int nmpc_path_queue_default(nmpc_path_queue* q)
 {
-    const TraceRange trace("nmpc_batch_node_tick");
+    if (!q) return set_err(NMPC_ERR_ARG, "path queue is NULL");
+    std::memset(q, 0, sizeof(*q));
+    q->part_length = 1000.0;  // NMPCNavControlROS.cpp:571
+    q->max_active_len = 5.0;  // nmpc_nav_control.yaml:6
+    return NMPC_OK;
+}
+
+namespace {
+
+// nmpc_batch_node_tick (q == nullptr) and nmpc_batch_node_tick_queue (q given, nseg unused)
+int node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_queue* q, unsigned char* mode,
+              const float* pose, const float* vel, const float* steer, const float* goal,
+              const nmpc_path_segment* segs, int seg_stride, const int* nseg, double* path_u, unsigned char* reset,
+              unsigned char* event, double* err, float* traj_out, int* n_solved, float* cmd, float* u0, int* status,
+              int* qp_iter, float* qp_res, void* stream)
+{
     // the checks that need no handle come first
     if (!np) return set_err(NMPC_ERR_ARG, "node params is NULL");
+    if (q) {
+        if (segs && !(q->npart && q->head && q->tail))
+            return set_err(NMPC_ERR_ARG, "path queue: npart, head and tail are required with segs");
+        if (!std::isfinite(q->part_length) || !std::isfinite(q->max_active_len))
+            return set_err(NMPC_ERR_ARG, "path queue: part_length and max_active_len must be finite");
+    }
     if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
     if (!mode) return set_err(NMPC_ERR_ARG, "mode is required");
     if (segs && seg_stride < 1) return set_err(NMPC_ERR_ARG, "seg_stride < 1");
@@ -898,7 +917,7 @@ int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsig
     if (B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
     if (B == 0) return NMPC_OK;
     if (!pose || !vel) return set_err(NMPC_ERR_ARG, "pose and vel are required");
-    const bool paths = segs && nseg && path_u;
+    const bool paths = segs && (q || nseg) && path_u;
     if (paths && node_gate_lds_bytes(b->prm.N) > 65536)
         return set_err(NMPC_ERR_UNSUPPORTED, "horizon too long for the gate's path march");
     hipStream_t s = (hipStream_t)stream;
@@ -925,8 +944,12 @@ int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsig
     g.pose = pose;
     g.goal = goal;
     g.segs = paths ? segs : nullptr;
-    g.nseg = paths ? nseg : nullptr;
+    g.nseg = (paths && !q) ? nseg : nullptr;
     g.path_u = paths ? path_u : nullptr;
+    if (q) {
+        g.queue = 1;
+        g.q = *q;
+    }
     g.event = event;
     g.err = err;
     g.traj = b->node_traj;
@@ -965,8 +988,34 @@ int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsig
     rc = hip_err(launch(b, a, kModeRun, s), "node_tick solve launch");
     if (rc) return rc;
     hipLaunchKernelGGL(k_node_finish, dim3((B + 255) / 256), dim3(256), 0, s, B, b->node_active, status, b->node_n,
-                       mode, event, reset, n_solved);
+                       mode, event, reset, n_solved, q ? q->remains : nullptr);
     return hip_err(hipGetLastError(), "node_finish launch");
+}
+
+}  // namespace
+
+int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsigned char* mode, const float* pose,
+                         const float* vel, const float* steer, const float* goal, const nmpc_path_segment* segs,
+                         int seg_stride, const int* nseg, double* path_u, unsigned char* reset, unsigned char* event,
+                         double* err, float* traj_out, int* n_solved, float* cmd, float* u0, int* status,
+                         int* qp_iter, float* qp_res, void* stream)
+{
+    const TraceRange trace("nmpc_batch_node_tick");
+    return node_tick(b, B, np, nullptr, mode, pose, vel, steer, goal, segs, seg_stride, nseg, path_u, reset, event,
+                     err, traj_out, n_solved, cmd, u0, status, qp_iter, qp_res, stream);
+}
+
+int nmpc_batch_node_tick_queue(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_queue* q,
+                               unsigned char* mode, const float* pose, const float* vel, const float* steer,
+                               const float* goal, const nmpc_path_segment* segs, int seg_stride, double* path_u,
+                               unsigned char* reset, unsigned char* event, double* err, float* traj_out,
+                               int* n_solved, float* cmd, float* u0, int* status, int* qp_iter, float* qp_res,
+                               void* stream)
+{
+    const TraceRange trace("nmpc_batch_node_tick_queue");
+    if (!q) return set_err(NMPC_ERR_ARG, "path queue is NULL");
+    return node_tick(b, B, np, q, mode, pose, vel, steer, goal, segs, seg_stride, nullptr, path_u, reset, event, err,
+                     traj_out, n_solved, cmd, u0, status, qp_iter, qp_res, stream);
 }
 
 int nmpc_batch_set_kernel(nmpc_batch* b, int kernel)

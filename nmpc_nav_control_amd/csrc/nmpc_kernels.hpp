@@ -151,6 +151,10 @@ struct NodeGateArgs {
     float* traj_out;
     float *cmd, *u0, *qp_res;
     int *status, *qp_iter;
+    // nmpc_batch_node_tick_queue: the robots' windows over their part lists (the kernels' Queue instantiations; nseg
+    // is not read then). 0: the plain tick, q unread
+    int queue;
+    nmpc_path_queue q;
 };
 hipError_t launch_node_gate(const NodeGateArgs& g, hipStream_t stream);
 size_t node_gate_lds_bytes(int N);

@@ -137,8 +137,10 @@ struct NearResult {
 //   px..pth  the robot's pose (fp32 widened exactly)
 //   lo_in, hi_in  caller's range bounds (NaN: none)
 //   holo     heading of the orientation error: 1 theta_holonomic, 0 theta (+ pi on a segment driven backwards)
-__device__ inline NearResult near_search(const nmpc_path_segment* S, int n, int j, double px, double py, double pth,
-                                         double lo_in, double hi_in, int holo)
+// (always inlined: the gate of the node tick calls it from two kernel instantiations, each of which keeps the code it
+// had as the only caller)
+__device__ __forceinline__ NearResult near_search(const nmpc_path_segment* S, int n, int j, double px, double py,
+                                                  double pth, double lo_in, double hi_in, int holo)
 {
     NearResult R;
     const double nan = __builtin_nan("");

@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import PathQueueStruct, check, lib
 from .controller import Pose
 
 SEG_DOUBLES = 16  # sizeof(nmpc_path_segment) / sizeof(double)
@@ -84,6 +84,67 @@ def pack_paths(path_lists, max_segs=None):
             segs[i, j] = s.pack()
         nseg[i] = len(pl)
     return segs, nseg
+
+
+class PathQueue:
+    """The path sets of B robots on the device, for BatchSolver.node_tick_queue (nmpc_path_queue): segs float64
+    [B][S][16] every robot's whole part list, npart int32 [B], and the window the tick keeps over it, head / tail
+    int32 [B] (active parts [head, tail), queued parts [tail, npart)) with path_u float64 [B], the progress relative
+    to part head. frames / lengths: also own frame int32 [B][S] (frame ids as numbers; a part joins the window only
+    behind a part of the same frame) and length float64 [B][S] (GetPathLength(); without it every part counts
+    part_length, the node's SetPathLength(1000)). remains float64 [B]: patch_remains of the robots in FOLLOW_PATH."""
+
+    def __init__(self, B, S, device="cuda", frames=False, lengths=False, remains=True, part_length=None,
+                 max_active_len=None):
+        self.B, self.S = int(B), int(S)
+        if self.S < 1:
+            raise ValueError("S must be >= 1")
+        self.device = torch.device(device)
+        z = lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=self.device)  # noqa: E731
+        self.segs = z(self.B, self.S, SEG_DOUBLES, dt=torch.float64)
+        self.npart, self.head, self.tail = (z(self.B, dt=torch.int32) for _ in range(3))
+        self.path_u = z(self.B, dt=torch.float64)
+        self.frame = z(self.B, self.S, dt=torch.int32) if frames else None
+        self.length = z(self.B, self.S, dt=torch.float64) if lengths else None
+        self.remains = torch.full((self.B,), math.nan, dtype=torch.float64, device=self.device) if remains else None
+        d = PathQueueStruct()
+        check(lib().nmpc_path_queue_default(ctypes.byref(d)), "nmpc_path_queue_default")
+        self.part_length = d.part_length if part_length is None else float(part_length)
+        self.max_active_len = d.max_active_len if max_active_len is None else float(max_active_len)
+
+    def set_path_set(self, i, parts, frames=None, lengths=None):
+        """Give robot i a new path set: parts is a list of PathSegment or an array [n][16] of segment records
+        (1 <= n <= S), frames / lengths its per-part frame ids and lengths (required when the queue owns those
+        arrays). Zeroes the robot's window and progress; the caller sets mode[i] = NODE_FOLLOW_PATH and
+        reset[i] = 1, as the node's path callbacks do."""
+        recs = np.stack([p.pack() if isinstance(p, PathSegment) else np.asarray(p, np.float64) for p in parts]) \
+            if len(parts) else np.zeros((0, SEG_DOUBLES))
+        n = len(recs)
+        if n > self.S or recs.shape[1:] != (SEG_DOUBLES,):
+            raise ValueError(f"robot {i}: {n} parts of shape {recs.shape[1:]} ({self.S} records of 16 doubles allowed)")
+        for name, own, given, dt in (("frames", self.frame, frames, np.int32), ("lengths", self.length, lengths,
+                                                                              np.float64)):
+            if (own is None) != (given is None):
+                raise ValueError(f"robot {i}: {name} must be given exactly when the queue owns them")
+            if own is not None:
+                a = np.asarray(given, dt)
+                if a.shape != (n,):
+                    raise ValueError(f"robot {i}: {name} must have one entry per part")
+                own[i, :n] = torch.from_numpy(a).to(self.device)
+        self.segs[i] = 0.0
+        if n:
+            self.segs[i, :n] = torch.from_numpy(recs).to(self.device)
+        self.npart[i] = n
+        self.head[i] = 0
+        self.tail[i] = 0
+        self.path_u[i] = 0.0
+
+    def struct(self):
+        """the nmpc_path_queue of this queue's tensors"""
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        return PathQueueStruct(npart=p(self.npart), head=p(self.head), tail=p(self.tail), frame=p(self.frame),
+                               length=p(self.length), part_length=self.part_length,
+                               max_active_len=self.max_active_len, remains=p(self.remains))
 
 
 def _dev_ptr(t, dtype):

@@ -16,9 +16,15 @@ away), the others Idle and scattered uniformly over the indices. In the same pro
 nearest + discretize + run over the full B, and over a batch holding just the active robots. Three interleaved
 rounds of each, the median; one JSON line per (B, fraction).
 
+With --mission: nmpc_batch_node_tick_queue, the node tick that keeps each robot's path-set queue on the device, on
+--node's fleet with every robot active (B = 4096 and 1024, diff): the queue tick on one-part sets against
+nmpc_batch_node_tick on the same paths (the cost of the queue), and the queue tick on three-part sets (each robot's
+path as the first part of a forward / reverse / forward set, so that the window logic has parts to look at). Five
+interleaved timed windows of each after a warm-up, median and spread; one JSON line per B.
+
 Poses of --nearest and --tick: the path points at the seeded nearest_u, displaced by a seeded offset of up to 0.1 m.
 
-usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick | --node]
+usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick | --node | --mission]
 """
 import argparse
 import json
@@ -118,7 +124,10 @@ def main(argv=None):
     ap.add_argument("--tick", action="store_true")
     ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--node", action="store_true")
+    ap.add_argument("--mission", action="store_true")
     a = ap.parse_args(argv)
+    if a.mission:
+        return mission_bench(a)
     if a.node:
         return node_bench(a)
     if a.nearest:
@@ -277,6 +286,83 @@ def node_bench(a):
                             active=int((small["st"] != 0).sum())),
                 form_B="%s w%d" % (plan_b["kernel"], plan_b["waves_per_robot"]),
                 form_active="%s w%d" % (plan_k["kernel"], plan_k["waves_per_robot"]))), flush=True)
+
+
+def mission_sets(segs, nseg):
+    """(plain one-part paths, one-part sets, three-part sets) of a seeded fleet: every robot's first segment alone,
+    and the same followed by its reversal (driven backwards) and itself again. Segment records [B][3][16]."""
+    B = len(nseg)
+    one = np.zeros((B, 3, SEG_DOUBLES))
+    one[:, 0] = segs[:, 0]
+    three = one.copy()
+    back = segs[:, 0].copy()
+    for o in (0, 4, 8):  # c(1 - u) of a cubic c(u), ascending coefficients
+        c0, c1, c2, c3 = (segs[:, 0, o + k] for k in range(4))
+        back[:, o], back[:, o + 1], back[:, o + 2], back[:, o + 3] = c0 + c1 + c2 + c3, -(c1 + 2 * c2 + 3 * c3), \
+            c2 + 3 * c3, -c3
+    back[:, 12] = -segs[:, 0, 12]
+    three[:, 1], three[:, 2] = back, segs[:, 0]
+    return one, three
+
+
+def mission_bench(a):
+    """the queue tick against the plain node tick (see the module docstring). Every handle runs warm-started ticks on
+    fixed measurements with path_u fed back, as --node does; `dropped` counts robots that left FollowPath."""
+    from nmpc_nav_control_amd._lib import NODE_FOLLOW_PATH
+    from nmpc_nav_control_amd.batch import BatchSolver, NodeParams
+    from nmpc_nav_control_amd.path import PathQueue
+    dev = torch.device("cuda:0")
+    N = a.num_poses - 1
+    npar = NodeParams.default()
+    stream = torch.cuda.current_stream()
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    for B in (4096, 1024):
+        segs, nseg, nu = seeded_paths(B)
+        nu = np.minimum(nu, 0.45)
+        ones = np.ones(B, np.int32)
+        pose = t(seeded_poses(segs, ones, nu))
+        one, three = mission_sets(segs, nseg)
+        vel = torch.zeros(3, B, device=dev)
+
+        def handle():
+            return dict(solver=BatchSolver("diff", N, B, device=dev), M=torch.full((B,), NODE_FOLLOW_PATH, dtype=torch.uint8, device=dev),
+                        u0=torch.zeros(2, B, device=dev), st=torch.zeros(B, dtype=torch.int32, device=dev))
+
+        plain, q1, q3 = handle(), handle(), handle()
+        plain.update(S=t(one), NS=t(ones), U=torch.zeros(B, dtype=torch.float64, device=dev))
+        for d, sets, n in ((q1, one, 1), (q3, three, 3)):
+            d["Q"] = PathQueue(B, 3, device=dev)
+            d["Q"].segs.copy_(t(sets))
+            d["Q"].npart.fill_(n)
+
+        def plain_step():
+            d = plain
+            d["solver"].node_tick(npar, d["M"], pose, vel, segs=d["S"], nseg=d["NS"], path_u=d["U"], u0=d["u0"],
+                                  status=d["st"])
+
+        def queue_step(d):
+            d["solver"].node_tick_queue(npar, d["Q"], d["M"], pose, vel, u0=d["u0"], status=d["st"])
+
+        steps = {"node_tick": plain_step, "queue_one_part": lambda: queue_step(q1),
+                 "queue_three_part": lambda: queue_step(q3)}
+        for fn in steps.values():  # warm-up: code objects, the handles' node buffers, the warm-started iterates
+            timed(fn, 10, stream)
+        ms = {k: [] for k in steps}
+        for _ in range(5):
+            for k, fn in steps.items():
+                ms[k].append(timed(fn, a.iters, stream))
+        med = {k: sorted(v)[2] for k, v in ms.items()}
+        same = all(torch.equal(plain[k], q1[k]) for k in ("u0", "st", "M")) and torch.equal(plain["U"], q1["Q"].path_u)
+        print(json.dumps(dict(
+            metric="mission tick ms (diff N=%d)" % N, B=B, node_tick_ms=round(med["node_tick"], 4),
+            queue_one_part_ms=round(med["queue_one_part"], 4), queue_three_part_ms=round(med["queue_three_part"], 4),
+            queue_over_node=round(med["queue_one_part"] / med["node_tick"], 4),
+            spread_ms={k: round(max(v) - min(v), 4) for k, v in ms.items()},
+            windows={k: [round(x, 4) for x in v] for k, v in ms.items()},
+            one_part_equals_node_tick=bool(same),
+            dropped={k: int((d["M"] != NODE_FOLLOW_PATH).sum()) for k, d in (("node", plain), ("one", q1), ("three", q3))},
+            failed={k: int((d["st"] != 0).sum()) for k, d in (("node", plain), ("one", q1), ("three", q3))},
+            window_three=[int(q3["Q"].head.max()), int(q3["Q"].tail.max())])), flush=True)
 
 
 if __name__ == "__main__":
