@@ -36,6 +36,13 @@ def _stream(stream):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+def _segs_stride(segs, B):
+    """Records per robot of segs, float64 [B][S][16] (the nmpc_path_segment layout)."""
+    if segs.dim() != 3 or segs.shape[0] != B or segs.shape[2] != 16:
+        raise ValueError(f"segs: expected shape ({B}, S, 16), got {tuple(segs.shape)}")
+    return segs.shape[1]
+
+
 class NodeParams:
     """nmpc_node_params (include/nmpc_amd/nmpc_batch.h): the node's thresholds, angles in radians. ``default()``
     is the shipped nmpc_nav_control.yaml; keyword arguments override fields (``NodeParams.default(max_pos_err=1.0)``)."""
@@ -181,11 +188,21 @@ class BatchSolver:
     def empty(self, *shape, dtype=torch.float32):
         return torch.empty(*shape, dtype=dtype, device=self.device)
 
-    def solve(self, x0, yref, We=None, reset=None, u0=None, x1=None, xtraj=None, utraj=None, status=None,
-              qp_iter=None, qp_res=None, stream=None):
-        B = x0.shape[1]
+    def _batch_of(self, t):
+        """B of a call, from its first [field][B] input."""
+        B = t.shape[1]
         if not 0 <= B <= self.capacity:
             raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        return B
+
+    def _outputs(self, B, cmd, u0, status, qp_iter, qp_res, stream):
+        """The trailing arguments of every run-mode entry point: the per-robot outputs and the stream."""
+        return (_ptr(cmd, F32, (3, B), "cmd"), _ptr(u0, F32, (self.nu, B), "u0"), _ptr(status, I32, (B,), "status"),
+                _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream))
+
+    def solve(self, x0, yref, We=None, reset=None, u0=None, x1=None, xtraj=None, utraj=None, status=None,
+              qp_iter=None, qp_res=None, stream=None):
+        B = self._batch_of(x0)
         ny_in = yref.shape[1]
         N, nx, nu = self.N, self.nx, self.nu
         check(lib().nmpc_batch_solve(
@@ -201,9 +218,7 @@ class BatchSolver:
         """nmpc_batch_solve with a caller-held iterate: xbar [(N+1)*NX][ld], ubar [N*NU][ld] are read and overwritten
         with the new iterate in place (nmpc_batch_solve_iterate). The IPM warm start still comes from the handle's
         slot i: keep instance i in slot i across calls, or call forget_warm after reordering."""
-        B = x0.shape[1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        B = self._batch_of(x0)
         ld = xbar.shape[1]
         if ubar.shape[1] != ld:
             raise ValueError("xbar and ubar need the same leading dimension")
@@ -218,36 +233,27 @@ class BatchSolver:
 
     def run(self, pose, vel, traj, steer=None, traj_len=None, reset=None, cmd=None, u0=None, status=None,
             qp_iter=None, qp_res=None, stream=None):
-        B = pose.shape[1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        B = self._batch_of(pose)
         check(lib().nmpc_batch_run(
             self._h, B, _ptr(pose, F32, (3, B), "pose"), _ptr(vel, F32, (3, B), "vel"),
             _ptr(steer, F32, (B,), "steer"), _ptr(traj, F32, (self.N + 1, 3, B), "traj"),
-            _ptr(traj_len, I32, (B,), "traj_len"), _ptr(reset, U8, (B,), "reset"), _ptr(cmd, F32, (3, B), "cmd"),
-            _ptr(u0, F32, (self.nu, B), "u0"), _ptr(status, I32, (B,), "status"),
-            _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)),
-            "nmpc_batch_run")
+            _ptr(traj_len, I32, (B,), "traj_len"), _ptr(reset, U8, (B,), "reset"),
+            *self._outputs(B, cmd, u0, status, qp_iter, qp_res, stream)), "nmpc_batch_run")
 
     def run_path(self, pose, vel, segs, nseg, nearest_u, sample_period, is_holonomic=False, steer=None, reset=None,
                  traj_out=None, cmd=None, u0=None, status=None, qp_iter=None, qp_res=None, stream=None):
         """processFollowPath's getNextNPoses + run for B robots in one launch (nmpc_batch_run_path): segs
         float64 [B][S][16] (the nmpc_path_segment layout, nmpc_nav_control_amd.path.pack_paths), nseg int32
         [B], nearest_u float64 [B]; traj_out [N+1][3][B] receives the poses."""
-        B = pose.shape[1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
-        if segs.dim() != 3 or segs.shape[0] != B or segs.shape[2] != 16:
-            raise ValueError(f"segs: expected shape ({B}, S, 16), got {tuple(segs.shape)}")
+        B = self._batch_of(pose)
+        stride = _segs_stride(segs, B)
         check(lib().nmpc_batch_run_path(
             self._h, B, _ptr(pose, F32, (3, B), "pose"), _ptr(vel, F32, (3, B), "vel"),
-            _ptr(steer, F32, (B,), "steer"), _ptr(segs, torch.float64, None, "segs"), segs.shape[1],
+            _ptr(steer, F32, (B,), "steer"), _ptr(segs, torch.float64, None, "segs"), stride,
             _ptr(nseg, I32, (B,), "nseg"), _ptr(nearest_u, torch.float64, (B,), "nearest_u"), float(sample_period),
             1 if is_holonomic else 0, _ptr(reset, U8, (B,), "reset"),
-            _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"), _ptr(cmd, F32, (3, B), "cmd"),
-            _ptr(u0, F32, (self.nu, B), "u0"), _ptr(status, I32, (B,), "status"),
-            _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)),
-            "nmpc_batch_run_path")
+            _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"),
+            *self._outputs(B, cmd, u0, status, qp_iter, qp_res, stream)), "nmpc_batch_run_path")
 
     def follow_path(self, pose, vel, segs, nseg, path_u, sample_period, is_holonomic=False, max_pos_err=float("inf"),
                     max_ori_err=float("inf"), steer=None, reset=None, err=None, off_path=None, traj_out=None, cmd=None,
@@ -257,21 +263,16 @@ class BatchSolver:
         progress so far; 0 on a new path) and overwritten with nearest_u; err float64 [2][B] receives
         {pos_error_to_path, ori_error_to_path}, off_path uint8 [B] the robots whose error reached max_pos_err /
         max_ori_err (their cmd is zeroed; inf or NaN: no check). Everything else as run_path."""
-        B = pose.shape[1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
-        if segs.dim() != 3 or segs.shape[0] != B or segs.shape[2] != 16:
-            raise ValueError(f"segs: expected shape ({B}, S, 16), got {tuple(segs.shape)}")
+        B = self._batch_of(pose)
+        stride = _segs_stride(segs, B)
         check(lib().nmpc_batch_follow_path(
             self._h, B, _ptr(pose, F32, (3, B), "pose"), _ptr(vel, F32, (3, B), "vel"),
-            _ptr(steer, F32, (B,), "steer"), _ptr(segs, torch.float64, None, "segs"), segs.shape[1],
+            _ptr(steer, F32, (B,), "steer"), _ptr(segs, torch.float64, None, "segs"), stride,
             _ptr(nseg, I32, (B,), "nseg"), _ptr(path_u, torch.float64, (B,), "path_u"), float(sample_period),
             1 if is_holonomic else 0, float(max_pos_err), float(max_ori_err), _ptr(reset, U8, (B,), "reset"),
             _ptr(err, torch.float64, (2, B), "err"), _ptr(off_path, U8, (B,), "off_path"),
-            _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"), _ptr(cmd, F32, (3, B), "cmd"),
-            _ptr(u0, F32, (self.nu, B), "u0"), _ptr(status, I32, (B,), "status"),
-            _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)),
-            "nmpc_batch_follow_path")
+            _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"),
+            *self._outputs(B, cmd, u0, status, qp_iter, qp_res, stream)), "nmpc_batch_follow_path")
 
     def node_tick(self, node_params, mode, pose, vel, goal=None, segs=None, nseg=None, path_u=None, steer=None,
                   reset=None, event=None, err=None, traj_out=None, n_solved=None, cmd=None, u0=None, status=None,
@@ -283,14 +284,8 @@ class BatchSolver:
         float64 [2][B] the path errors (NaN for the others), traj_out the references of the solving robots (NaN for
         the others), n_solved int32 [1] their count. Robots that do not solve keep their resident state bit for bit
         and get zero outputs. node_params: a NodeParams."""
-        B = pose.shape[1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
-        stride = 1
-        if segs is not None:
-            if segs.dim() != 3 or segs.shape[0] != B or segs.shape[2] != 16:
-                raise ValueError(f"segs: expected shape ({B}, S, 16), got {tuple(segs.shape)}")
-            stride = segs.shape[1]
+        B = self._batch_of(pose)
+        stride = _segs_stride(segs, B) if segs is not None else 1
         check(lib().nmpc_batch_node_tick(
             self._h, B, ctypes.byref(node_params.c), _ptr(mode, torch.uint8, (B,), "mode"),
             _ptr(pose, F32, (3, B), "pose"), _ptr(vel, F32, (3, B), "vel"), _ptr(steer, F32, (B,), "steer"),
@@ -298,9 +293,8 @@ class BatchSolver:
             _ptr(nseg, I32, (B,), "nseg"), _ptr(path_u, torch.float64, (B,), "path_u"),
             _ptr(reset, torch.uint8, (B,), "reset"), _ptr(event, torch.uint8, (B,), "event"),
             _ptr(err, torch.float64, (2, B), "err"), _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"),
-            _ptr(n_solved, I32, (1,), "n_solved"), _ptr(cmd, F32, (3, B), "cmd"), _ptr(u0, F32, (self.nu, B), "u0"),
-            _ptr(status, I32, (B,), "status"), _ptr(qp_iter, I32, (B,), "qp_iter"),
-            _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)), "nmpc_batch_node_tick")
+            _ptr(n_solved, I32, (1,), "n_solved"), *self._outputs(B, cmd, u0, status, qp_iter, qp_res, stream)),
+            "nmpc_batch_node_tick")
 
     def node_tick_queue(self, node_params, queue, mode, pose, vel, goal=None, steer=None, reset=None, event=None,
                         err=None, traj_out=None, n_solved=None, cmd=None, u0=None, status=None, qp_iter=None,
@@ -310,9 +304,7 @@ class BatchSolver:
         remains when it was built with them); the tick pops the parts behind each FOLLOW_PATH robot, extends its
         active window, and at the end of a part hops to the next queued one (event NODE_EV_NEXT_PART). Everything
         else as node_tick."""
-        B = pose.shape[1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        B = self._batch_of(pose)
         if queue.B != B:
             raise ValueError(f"queue: built for {queue.B} robots, the tick has {B}")
         check(lib().nmpc_batch_node_tick_queue(
@@ -323,14 +315,10 @@ class BatchSolver:
             _ptr(queue.path_u, torch.float64, (B,), "path_u"), _ptr(reset, torch.uint8, (B,), "reset"),
             _ptr(event, torch.uint8, (B,), "event"), _ptr(err, torch.float64, (2, B), "err"),
             _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"), _ptr(n_solved, I32, (1,), "n_solved"),
-            _ptr(cmd, F32, (3, B), "cmd"), _ptr(u0, F32, (self.nu, B), "u0"), _ptr(status, I32, (B,), "status"),
-            _ptr(qp_iter, I32, (B,), "qp_iter"), _ptr(qp_res, F32, (3, B), "qp_res"), _stream(stream)),
-            "nmpc_batch_node_tick_queue")
+            *self._outputs(B, cmd, u0, status, qp_iter, qp_res, stream)), "nmpc_batch_node_tick_queue")
 
     def fleet_sim_step(self, path, s, pose, vel, steer, u0, status, traj, traj_len, advance=True, stream=None):
-        B = pose.shape[1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        B = self._batch_of(pose)
         check(lib().nmpc_fleet_sim_step(
             self._h, B, _ptr(path, F32, (6, B), "path"), _ptr(s, F32, (B,), "s"), _ptr(pose, F32, (3, B), "pose"),
             _ptr(vel, F32, (3, B), "vel"), _ptr(steer, F32, (B,), "steer"), _ptr(u0, F32, (self.nu, B), "u0"),
@@ -346,9 +334,7 @@ class BatchSolver:
         same launch accumulates the last solve's statistics into (nmpc_fleet_stats): qp_iter int32 [B] (in),
         iters_sum int64 [B], iters_max int32 [B], fail_cnt int64 [B], hist int64 [64], cold_cnt / cold_iters
         int64 [B]."""
-        B = pose.shape[1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        B = self._batch_of(pose)
         S = None
         if stats is not None:
             S = FleetStats(qp_iter=_ptr(stats["qp_iter"], I32, (B,), "qp_iter"),

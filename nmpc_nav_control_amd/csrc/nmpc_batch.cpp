@@ -87,14 +87,26 @@ int hip_err(hipError_t e, const char* what)
     return set_err(NMPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-bool dims_of(int model, int* nx, int* nu, int* nbx, int* nbu, int* np)
+// The one model switch: f(M{}) with the model's type (nmpc_models.hpp), whose result every M must give in one type.
+// The id was checked (dims_of) wherever it came from outside
+template <class F>
+auto with_model(int model, F&& f)
 {
     switch (model) {
-    case NMPC_MODEL_DIFF2AMR: *nx = 7; *nu = 2; *nbx = 2; *nbu = 2; *np = 2; return true;
-    case NMPC_MODEL_OMNI4AMR: *nx = 11; *nu = 4; *nbx = 4; *nbu = 4; *np = 2; return true;
-    case NMPC_MODEL_TRIC3AMR: *nx = 7; *nu = 2; *nbx = 2; *nbu = 2; *np = 3; return true;
-    default: return false;
+    case NMPC_MODEL_DIFF2AMR: return f(Diff2{});
+    case NMPC_MODEL_OMNI4AMR: return f(Omni4{});
+    default: return f(Tric3{});
     }
+}
+
+bool dims_of(int model, int* nx, int* nu, int* nbx, int* nbu, int* np)
+{
+    if (model != NMPC_MODEL_DIFF2AMR && model != NMPC_MODEL_OMNI4AMR && model != NMPC_MODEL_TRIC3AMR) return false;
+    with_model(model, [&](auto m) {
+        using M = decltype(m);
+        *nx = M::NX; *nu = M::NU; *nbx = M::NBX; *nbu = M::NBU; *np = M::NP;
+    });
+    return true;
 }
 
 KParams to_kparams(const nmpc_model_params& p, int nx, int nu, int nbx, int nbu)
@@ -142,11 +154,7 @@ KParams to_kparams(const nmpc_model_params& p, int nx, int nu, int nbx, int nbu)
 
 size_t scratch_floats(int model, int N, int stride)
 {
-    switch (model) {
-    case NMPC_MODEL_DIFF2AMR: return team_scratch_floats<Diff2>(N, stride);
-    case NMPC_MODEL_OMNI4AMR: return team_scratch_floats<Omni4>(N, stride);
-    default: return team_scratch_floats<Tric3>(N, stride);
-    }
+    return with_model(model, [&](auto m) { return team_scratch_floats<decltype(m)>(N, stride); });
 }
 
 template <class M>
@@ -193,22 +201,23 @@ inline size_t rowpar_lds_cap(const nmpc_batch* b, int B)
     return b->lds_per_cu / (size_t)(per_cu > 0 ? per_cu : 1);
 }
 
+// Whether a launch of B robots (path_march: a run_path launch, whose march only the team kernel has) runs the
+// row-parallel kernel: its horizon segments (0: the serial phases), or -1 for the team kernel
 template <class M>
-bool rowpar_ok(const nmpc_batch* b, KArgs& a, int mode)
+int rowpar_ok(const nmpc_batch* b, int B, bool path_march, int mode)
 {
-    if (b->kp.ipm != NMPC_IPM_SINGLE || a.segs || a.B > b->rowpar_max) return false;
-    const int rows = a.B <= 256 ? 16 : b->seg_rows;  // segments: any row up to 256 robots, the first wave's above
-    const size_t cap = rowpar_lds_cap(b, a.B);
+    if (b->kp.ipm != NMPC_IPM_SINGLE || path_march || B > b->rowpar_max) return -1;
+    const int rows = B <= 256 ? 16 : b->seg_rows;  // segments: any row up to 256 robots, the first wave's above
+    const size_t cap = rowpar_lds_cap(b, B);
     int S = b->seg >= 0 ? b->seg : seg_count(b->prm.N, rows);
     if (S > rows || S > kSegMax || (S > 0 && b->prm.N % S)) S = 0;
     if (S > 0 && rowpar_lds_bytes<M>(b->prm.N, mode, S) > cap) S = 0;
-    if (a.B > 256 && S == 0 && b->seg < 0) return false;  // one wave per robot only with segments (auto)
+    if (B > 256 && S == 0 && b->seg < 0) return -1;  // one wave per robot only with segments (auto)
     // above 256 robots two robots' waves share a SIMD, which needs <= 256 registers per lane: diff and tric's
     // segmented kernels take 246-250, omni4's (11 x 11 master blocks) 357 (tools/reg_usage.py), so omni4 keeps the
     // team kernel there
-    if (a.B > 256 && M::NU == 4 && b->rowpar_max <= 1024) return false;
-    a.seg = S;
-    return rowpar_lds_bytes<M>(b->prm.N, mode, S) <= cap;
+    if (B > 256 && M::NU == 4 && b->rowpar_max <= 1024) return -1;
+    return rowpar_lds_bytes<M>(b->prm.N, mode, S) <= cap ? S : -1;
 }
 
 // Records one sweep of the team kernel touches over the handle's capacity in the wide layout (9 or 16 slots of
@@ -236,37 +245,54 @@ int rec_layout_auto(const nmpc_batch* b)
 }
 
 // the warm-flag tag of a launch (NMPC_WARM_TAG_*): its multipliers' record layout and field order
-int warm_tag_of(const nmpc_batch* b, const KArgs& a)
+int warm_tag_of(const nmpc_batch* b, int rec_split)
 {
     if (b->kp.ipm != NMPC_IPM_SINGLE) return NMPC_WARM_TAG_MEHROTRA;
-    return a.rec_split ? NMPC_WARM_TAG_SPLIT : NMPC_WARM_TAG_WIDE;
+    return rec_split ? NMPC_WARM_TAG_SPLIT : NMPC_WARM_TAG_WIDE;
 }
 
-// Kernel choice, record layout and (team kernel) placement before a launch (schedule.hip); fills a.order /
-// a.iter_key. Every robot's warm flag carries the tag of the layout its multipliers sit in, so a launch whose
-// layout differs from a robot's last one starts that robot cold and leaves the others alone
+// What a launch of B robots runs: the kernel (waves per robot of k_sqp_rti_rowpar, 0: the team kernel), the
+// row-parallel kernel's horizon segments, the team kernel's record layout and the tag the launch leaves in the warm
+// flags. schedule() launches from it and nmpc_batch_plan_ex reports it; nothing else decides any of the four
+struct LaunchPlan {
+    int waves, seg, rec_split, warm_tag;
+};
+
+LaunchPlan plan_launch(const nmpc_batch* b, int B, bool path_march, int mode)
+{
+    LaunchPlan p{};
+    const int S = with_model(b->prm.model, [&](auto m) { return rowpar_ok<decltype(m)>(b, B, path_march, mode); });
+    if (S >= 0) {
+        p.waves = rowpar_waves(b, B);
+        p.seg = S;
+    }
+    // the row-parallel kernel keeps the wide single-direction records; the team kernel the handle's layout
+    p.rec_split = (!p.waves && b->kp.ipm == NMPC_IPM_SINGLE) ? b->rec_split : 0;
+    p.warm_tag = warm_tag_of(b, p.rec_split);
+    return p;
+}
+
+// The launch's plan and (team kernel) placement before a launch (schedule.hip); fills a.order / a.iter_key. Every
+// robot's warm flag carries the tag of the layout its multipliers sit in, so a launch whose layout differs from a
+// robot's last one starts that robot cold and leaves the others alone
 hipError_t schedule(nmpc_batch* b, KArgs& a, int mode, hipStream_t s)
 {
+    const LaunchPlan p = plan_launch(b, a.B, a.segs != nullptr, mode);
     a.iter_key = b->iter_key;
     a.warm = b->warm;
-    switch (b->prm.model) {
-    case NMPC_MODEL_DIFF2AMR: a.rowpar = rowpar_ok<Diff2>(b, a, mode); break;
-    case NMPC_MODEL_OMNI4AMR: a.rowpar = rowpar_ok<Omni4>(b, a, mode); break;
-    default: a.rowpar = rowpar_ok<Tric3>(b, a, mode); break;
-    }
-    if (a.rowpar) a.rowpar = rowpar_waves(b, a.B);  // waves per robot
-    // the row-parallel kernel keeps the wide single-direction records; the team kernel the handle's layout
-    a.rec_split = (!a.rowpar && b->kp.ipm == NMPC_IPM_SINGLE) ? b->rec_split : 0;
-    a.warm_tag = warm_tag_of(b, a);
+    a.rowpar = p.waves;
+    a.seg = p.seg;
+    a.rec_split = p.rec_split;
+    a.warm_tag = p.warm_tag;
     if (a.rowpar && !a.n_active) return hipSuccess;  // one robot per wave: nothing to place
     a.dense = ((a.B + 3) / 4 > b->n_simd) ? 1 : 0;  // 4 teams per wave
     // small batches leave most of the chip idle: one wave per robot, whose spare rows integrate P0's stages
     a.split = (!a.dense && a.B <= b->split_max) ? 1 : 0;
+    int layout = b->sched;
+    if (layout == NMPC_SCHED_AUTO) layout = a.dense ? NMPC_SCHED_SORTED : NMPC_SCHED_OFF;
     if (a.n_active) {
         // node tick: every form takes the compacted order (the robots that solve first). The forms with one robot
         // per block keep index order; the team kernel follows the handle's schedule (interleaved and spread: sorted)
-        int layout = b->sched;
-        if (layout == NMPC_SCHED_AUTO) layout = a.dense ? NMPC_SCHED_SORTED : NMPC_SCHED_OFF;
         if (a.rowpar) a.dense = a.split = 0;
         const int sorted = (!a.rowpar && !a.split && layout != NMPC_SCHED_OFF) ? 1 : 0;
         a.order = b->order;
@@ -275,15 +301,13 @@ hipError_t schedule(nmpc_batch* b, KArgs& a, int mode, hipStream_t s)
     if (a.split) return hipSuccess;  // one robot per wave: nothing to place
 #ifdef NMPC_HYBRID
     // (the hybrid launch mixes the kernels in one tick: only where they share the record layout)
-    if (b->hybrid_h > 0 && b->kp.ipm == NMPC_IPM_SINGLE && !a.segs && b->hyb_n && a.rec_split == 0) {
+    if (b->hybrid_h > 0 && b->kp.ipm == NMPC_IPM_SINGLE && !a.segs && b->hyb_n && p.rec_split == 0) {
         a.hyb_role = 1;  // launch() adds the segmented part on the aux stream
         a.hyb_n = b->hyb_n;
         a.order = b->order;
         return launch_hybrid_order(b->iter_key, a.B, b->hybrid_h, b->hybrid_cap, b->order, b->hyb_n, s);
     }
 #endif
-    int layout = b->sched;
-    if (layout == NMPC_SCHED_AUTO) layout = a.dense ? NMPC_SCHED_SORTED : NMPC_SCHED_OFF;
     if (layout == NMPC_SCHED_OFF) return hipSuccess;
     a.order = b->order;
     return launch_team_order(b->iter_key, a.B, layout, b->sorted, b->order, s);
@@ -322,72 +346,50 @@ hipError_t launch(nmpc_batch* b, KArgs& a, int mode, hipStream_t s)
     const hipError_t e = schedule(b, a, mode, s);
     if (e != hipSuccess) return e;
 #ifdef NMPC_HYBRID
-    if (a.hyb_role == 1) {
-        switch (b->prm.model) {
-        case NMPC_MODEL_DIFF2AMR: return launch_hybrid<Diff2>(b, a, mode, s);
-        case NMPC_MODEL_OMNI4AMR: return launch_hybrid<Omni4>(b, a, mode, s);
-        default: return launch_hybrid<Tric3>(b, a, mode, s);
-        }
-    }
+    if (a.hyb_role == 1)
+        return with_model(b->prm.model, [&](auto m) { return launch_hybrid<decltype(m)>(b, a, mode, s); });
 #endif
-    switch (b->prm.model) {
-    case NMPC_MODEL_DIFF2AMR: return launch_m<Diff2>(b, a, mode, s);
-    case NMPC_MODEL_OMNI4AMR: return launch_m<Omni4>(b, a, mode, s);
-    default: return launch_m<Tric3>(b, a, mode, s);
-    }
+    return with_model(b->prm.model, [&](auto m) { return launch_m<decltype(m)>(b, a, mode, s); });
 }
 
-__global__ void k_init_iterate(float* xbar, float* ubar, float* carried, unsigned char* warm, int B, int stride, int N,
-                               int nx, int nu, int nbx, int mode)
+// the handle and batch-size checks every entry point of a handle starts with
+int check_batch(const nmpc_batch* b, int B)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B) return;
-    warm[i] = 0;  // the next solve starts its IPM cold
-    for (int k = 0; k <= N; k++)
-        for (int j = 0; j < nx; j++)
-            xbar[((size_t)k * nx + j) * stride + i] = (mode == 0 && j == 2) ? 3.14159265358979323846f : 0.0f;
-    for (int k = 0; k < N; k++)
-        for (int j = 0; j < nu; j++) ubar[((size_t)k * nu + j) * stride + i] = 0.0f;
-    // create semantics start the wrapper's x0 vel-refs at zero (the member struct is value-initialised); a reset
-    // (reset_mpc -> {name}_acados_reset) leaves them, as the reference does and as the solve's reset mask does
-    if (mode == 0)
-        for (int j = 0; j < nbx; j++) carried[(size_t)j * stride + i] = 0.0f;
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    return NMPC_OK;
 }
 
-__global__ void k_forget_warm(unsigned char* warm, const unsigned char* mask, int B)
+// a launch of B robots on the handle's resident state; the entry points add the fields that are theirs
+KArgs resident_args(const nmpc_batch* b, int B)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < B && (!mask || mask[i])) warm[i] = 0;
+    KArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.stride = b->capacity;
+    a.sstride = b->capacity;
+    a.xbar = b->xbar;
+    a.ubar = b->ubar;
+    a.carried = b->carried;
+    a.scratch = b->scratch;
+    return a;
 }
 
-// the path-error check of a FollowPath tick (NMPCNavControlROS.cpp:658-660): a robot whose position or orientation
-// error reaches its threshold is flagged and gets the stop command; use_pos / use_ori: the comparison is on
-__global__ void k_path_guard(int B, const double* err, double max_pos, double max_ori, int use_pos, int use_ori,
-                             unsigned char* off_path, float* cmd)
+// ... with the inputs and outputs every run-mode launch has; the reference (traj or the path march) is the caller's
+KArgs run_args(const nmpc_batch* b, int B, const float* pose, const float* vel, const float* steer,
+               const unsigned char* reset, float* cmd, float* u0, int* status, int* qp_iter, float* qp_res)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B) return;
-    const bool off = (use_pos && err[i] >= max_pos) || (use_ori && err[(size_t)B + i] >= max_ori);
-    if (off_path) off_path[i] = off ? 1 : 0;
-    if (off && cmd)
-        for (int j = 0; j < 3; j++) cmd[(size_t)j * B + i] = 0.0f;
-}
-
-// after a node tick's solve launch: a robot that solved has consumed its pending reset, and a failed solve sends it
-// to Error (NMPCNavControlROS.cpp:716-719); n_solved receives the active count
-__global__ void k_node_finish(int B, const unsigned char* active, const int* status, const int* n_active,
-                              unsigned char* mode, unsigned char* event, unsigned char* reset, int* n_solved,
-                              double* remains)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0 && n_solved) n_solved[0] = n_active[0];
-    if (i >= B || !active[i]) return;
-    if (reset) reset[i] = 0;
-    if (status[i] != 0) {
-        mode[i] = NMPC_NODE_ERROR;
-        if (event) event[i] = NMPC_NODE_EV_SOLVE_FAILED;
-        if (remains) remains[i] = __builtin_nan("");  // (node_tick_queue: no longer in FollowPath)
-    }
+    KArgs a = resident_args(b, B);
+    a.pose = pose;
+    a.vel = vel;
+    a.steer = steer;
+    a.reset = reset;
+    a.cmd = cmd;
+    a.u0 = u0;
+    a.status = status;
+    a.qp_iter = qp_iter;
+    a.qp_res = qp_res;
+    return a;
 }
 
 int check_params(const nmpc_model_params* prm)
@@ -644,13 +646,11 @@ int nmpc_batch_get_params(const nmpc_batch* b, nmpc_model_params* prm)
 
 int nmpc_batch_init_iterate(nmpc_batch* b, int B, int mode, void* stream)
 {
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (const int rc = check_batch(b, B)) return rc;
     if (mode != 0 && mode != 1) return set_err(NMPC_ERR_ARG, "mode must be 0 (create) or 1 (reset)");
-    if (B == 0) return NMPC_OK;
-    hipLaunchKernelGGL(k_init_iterate, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, b->xbar, b->ubar,
-                       b->carried, b->warm, B, b->capacity, b->prm.N, b->nx, b->nu, b->nbx, mode);
-    return hip_err(hipGetLastError(), "init_iterate launch");
+    return hip_err(launch_init_iterate(b->xbar, b->ubar, b->carried, b->warm, B, b->capacity, b->prm.N, b->nx, b->nu,
+                                       b->nbx, mode, (hipStream_t)stream),
+                   "init_iterate launch");
 }
 
 int nmpc_batch_solve(nmpc_batch* b, int B, const float* x0, const float* yref, int ny_in, const float* We,
@@ -658,20 +658,11 @@ int nmpc_batch_solve(nmpc_batch* b, int B, const float* x0, const float* yref, i
                      int* qp_iter, float* qp_res, void* stream)
 {
     const TraceRange trace("nmpc_batch_solve");
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (const int rc = check_batch(b, B)) return rc;
     if (B == 0) return NMPC_OK;
     if (!x0 || !yref) return set_err(NMPC_ERR_ARG, "x0 and yref are required");
     if (ny_in < 1 || ny_in > b->ny) return set_err(NMPC_ERR_ARG, "ny_in out of range [1, NY]");
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.B = B;
-    a.stride = b->capacity;
-    a.sstride = b->capacity;
-    a.xbar = b->xbar;
-    a.ubar = b->ubar;
-    a.carried = b->carried;
-    a.scratch = b->scratch;
+    KArgs a = resident_args(b, B);
     a.x0 = x0;
     a.yref = yref;
     a.ny_in = ny_in;
@@ -692,21 +683,15 @@ int solve_iterate(nmpc_batch* b, int B, const float* x0, const float* yref, int 
                   const unsigned char* reset, float* xbar, float* ubar, int ld, int* status, int* qp_iter,
                   float* qp_res, void* stream, const nmpc_stage_io* io)
 {
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (const int rc = check_batch(b, B)) return rc;
     if (B == 0) return NMPC_OK;
     if (!x0 || !yref || !xbar || !ubar) return set_err(NMPC_ERR_ARG, "x0, yref, xbar and ubar are required");
     if (ld < B) return set_err(NMPC_ERR_ARG, "ld < B");
     if (ny_in < 1 || ny_in > b->ny) return set_err(NMPC_ERR_ARG, "ny_in out of range [1, NY]");
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.B = B;
-    a.stride = ld;
-    a.sstride = b->capacity;  // the scratch planes follow the allocation, not the caller's ld
+    KArgs a = resident_args(b, B);
+    a.stride = ld;  // the caller's iterate; sstride stays: the scratch planes follow the allocation, not ld
     a.xbar = xbar;
     a.ubar = ubar;
-    a.carried = b->carried;  // run mode only
-    a.scratch = b->scratch;
     a.x0 = x0;
     a.yref = yref;
     a.ny_in = ny_in;
@@ -717,9 +702,7 @@ int solve_iterate(nmpc_batch* b, int B, const float* x0, const float* yref, int 
     a.qp_res = qp_res;
     if (io) {
         // one robot on the row-parallel kernel only (the team kernel does not stage)
-        nmpc_launch_plan plan{};
-        nmpc_batch_plan_ex(b, B, NMPC_PLAN_SOLVE, &plan);
-        if (B != 1 || plan.kernel != 1)
+        if (B != 1 || !plan_launch(b, B, false, kModeSolve).waves)
             return set_err(NMPC_ERR_ARG, "staged I/O needs a one-robot row-parallel launch");
         a.stage_in_h = io->in_h;
         a.stage_in_d = io->in_d;
@@ -755,30 +738,12 @@ int nmpc_batch_run(nmpc_batch* b, int B, const float* pose, const float* vel, co
                    int* status, int* qp_iter, float* qp_res, void* stream)
 {
     const TraceRange trace("nmpc_batch_run");
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (const int rc = check_batch(b, B)) return rc;
     if (B == 0) return NMPC_OK;
     if (!pose || !vel || !traj) return set_err(NMPC_ERR_ARG, "pose, vel and traj are required");
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.B = B;
-    a.stride = b->capacity;
-    a.sstride = b->capacity;
-    a.xbar = b->xbar;
-    a.ubar = b->ubar;
-    a.carried = b->carried;
-    a.scratch = b->scratch;
-    a.pose = pose;
-    a.vel = vel;
-    a.steer = steer;
+    KArgs a = run_args(b, B, pose, vel, steer, reset, cmd, u0, status, qp_iter, qp_res);
     a.traj = traj;
     a.traj_len = traj_len;
-    a.reset = reset;
-    a.cmd = cmd;
-    a.u0 = u0;
-    a.status = status;
-    a.qp_iter = qp_iter;
-    a.qp_res = qp_res;
     return hip_err(launch(b, a, kModeRun, (hipStream_t)stream), "run launch");
 }
 
@@ -788,8 +753,7 @@ int nmpc_batch_run_path(nmpc_batch* b, int B, const float* pose, const float* ve
                         float* cmd, float* u0, int* status, int* qp_iter, float* qp_res, void* stream)
 {
     const TraceRange trace("nmpc_batch_run_path");
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (const int rc = check_batch(b, B)) return rc;
     if (B == 0) return NMPC_OK;
     if (!pose || !vel || !segs || !nseg || !nearest_u)
         return set_err(NMPC_ERR_ARG, "pose, vel, segs, nseg and nearest_u are required");
@@ -797,18 +761,7 @@ int nmpc_batch_run_path(nmpc_batch* b, int B, const float* pose, const float* ve
     if (!(sample_period >= 0.0)) return set_err(NMPC_ERR_ARG, "sample_period must be >= 0");
     if (16 * (sizeof(double) + 3 * sizeof(float)) * (size_t)(b->prm.N + 1) > 65536)
         return set_err(NMPC_ERR_UNSUPPORTED, "horizon too long for the in-kernel path march");
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.B = B;
-    a.stride = b->capacity;
-    a.sstride = b->capacity;
-    a.xbar = b->xbar;
-    a.ubar = b->ubar;
-    a.carried = b->carried;
-    a.scratch = b->scratch;
-    a.pose = pose;
-    a.vel = vel;
-    a.steer = steer;
+    KArgs a = run_args(b, B, pose, vel, steer, reset, cmd, u0, status, qp_iter, qp_res);
     a.segs = segs;
     a.seg_stride = seg_stride;
     a.nseg = nseg;
@@ -816,12 +769,6 @@ int nmpc_batch_run_path(nmpc_batch* b, int B, const float* pose, const float* ve
     a.period = sample_period;
     a.holo = is_holonomic ? 1 : 0;
     a.traj_out = traj_out;
-    a.reset = reset;
-    a.cmd = cmd;
-    a.u0 = u0;
-    a.status = status;
-    a.qp_iter = qp_iter;
-    a.qp_res = qp_res;
     return hip_err(launch(b, a, kModeRun, (hipStream_t)stream), "run_path launch");
 }
 
@@ -832,8 +779,7 @@ int nmpc_batch_follow_path(nmpc_batch* b, int B, const float* pose, const float*
                            float* cmd, float* u0, int* status, int* qp_iter, float* qp_res, void* stream)
 {
     const TraceRange trace("nmpc_batch_follow_path");
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (const int rc = check_batch(b, B)) return rc;
     if (B == 0) return NMPC_OK;
     if (!pose || !vel || !segs || !nseg || !path_u)
         return set_err(NMPC_ERR_ARG, "pose, vel, segs, nseg and path_u are required");
@@ -860,9 +806,8 @@ int nmpc_batch_follow_path(nmpc_batch* b, int B, const float* pose, const float*
     rc = nmpc_batch_run_path(b, B, pose, vel, steer, segs, seg_stride, nseg, path_u, sample_period, is_holonomic,
                              reset, traj_out, cmd, u0, status, qp_iter, qp_res, stream);
     if (rc || !guard) return rc;
-    hipLaunchKernelGGL(k_path_guard, dim3((B + 255) / 256), dim3(256), 0, s, B, err, max_pos_err, max_ori_err, use_pos,
-                       use_ori, off_path, cmd);
-    return hip_err(hipGetLastError(), "path_guard launch");
+    return hip_err(launch_path_guard(B, err, max_pos_err, max_ori_err, use_pos, use_ori, off_path, cmd, s),
+                   "path_guard launch");
 }
 
 int nmpc_node_params_default(nmpc_node_params* np)
@@ -913,8 +858,7 @@ int node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_
     if (segs && seg_stride < 1) return set_err(NMPC_ERR_ARG, "seg_stride < 1");
     if (!std::isfinite(np->sample_period) || np->sample_period < 0.0)
         return set_err(NMPC_ERR_ARG, "sample_period must be finite and >= 0");
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (const int rc = check_batch(b, B)) return rc;
     if (B == 0) return NMPC_OK;
     if (!pose || !vel) return set_err(NMPC_ERR_ARG, "pose and vel are required");
     const bool paths = segs && (q || nseg) && path_u;
@@ -964,32 +908,15 @@ int node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_
     int rc = hip_err(launch_node_gate(g, s), "node_gate launch");
     if (rc) return rc;
     // nmpc_batch_run's launch on the gate's references, for the compacted robots
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.B = B;
-    a.stride = b->capacity;
-    a.sstride = b->capacity;
-    a.xbar = b->xbar;
-    a.ubar = b->ubar;
-    a.carried = b->carried;
-    a.scratch = b->scratch;
-    a.pose = pose;
-    a.vel = vel;
-    a.steer = steer;
+    KArgs a = run_args(b, B, pose, vel, steer, reset, cmd, u0, status, qp_iter, qp_res);
     a.traj = b->node_traj;
     a.traj_len = b->node_len;
-    a.reset = reset;
-    a.cmd = cmd;
-    a.u0 = u0;
-    a.status = status;
-    a.qp_iter = qp_iter;
-    a.qp_res = qp_res;
     a.n_active = b->node_n;
     rc = hip_err(launch(b, a, kModeRun, s), "node_tick solve launch");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_node_finish, dim3((B + 255) / 256), dim3(256), 0, s, B, b->node_active, status, b->node_n,
-                       mode, event, reset, n_solved, q ? q->remains : nullptr);
-    return hip_err(hipGetLastError(), "node_finish launch");
+    return hip_err(launch_node_finish(B, b->node_active, status, b->node_n, mode, event, reset, n_solved,
+                                      q ? q->remains : nullptr, s),
+                   "node_finish launch");
 }
 
 }  // namespace
@@ -1045,11 +972,8 @@ int nmpc_batch_state(nmpc_batch* b, float** xbar, float** ubar, float** carried,
 
 int nmpc_batch_forget_warm(nmpc_batch* b, int B, const unsigned char* mask, void* stream)
 {
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
-    if (B == 0) return NMPC_OK;
-    hipLaunchKernelGGL(k_forget_warm, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, b->warm, mask, B);
-    return hip_err(hipGetLastError(), "forget_warm launch");
+    if (const int rc = check_batch(b, B)) return rc;
+    return hip_err(launch_forget_warm(b->warm, mask, B, (hipStream_t)stream), "forget_warm launch");
 }
 
 int nmpc_batch_set_record_layout(nmpc_batch* b, int layout)
@@ -1071,25 +995,13 @@ int nmpc_batch_plan_ex(const nmpc_batch* b, int B, int mode, nmpc_launch_plan* p
     if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range");
     if (mode != NMPC_PLAN_SOLVE && mode != NMPC_PLAN_RUN && mode != NMPC_PLAN_RUN_PATH)
         return set_err(NMPC_ERR_ARG, "mode must be NMPC_PLAN_SOLVE, NMPC_PLAN_RUN or NMPC_PLAN_RUN_PATH");
-    KArgs a{};
-    a.B = B;
-    // run_path launches carry the path segments (a.segs), which keep them on the team kernel
-    static const nmpc_path_segment kSeg{};
-    if (mode == NMPC_PLAN_RUN_PATH) a.segs = &kSeg;
-    const int km = mode == NMPC_PLAN_SOLVE ? kModeSolve : kModeRun;
-    bool rp;
-    switch (b->prm.model) {
-    case NMPC_MODEL_DIFF2AMR: rp = rowpar_ok<Diff2>(b, a, km); break;
-    case NMPC_MODEL_OMNI4AMR: rp = rowpar_ok<Omni4>(b, a, km); break;
-    default: rp = rowpar_ok<Tric3>(b, a, km); break;
-    }
-    a.rowpar = rp ? 1 : 0;
-    a.rec_split = (!rp && b->kp.ipm == NMPC_IPM_SINGLE) ? b->rec_split : 0;
-    plan->kernel = rp ? 1 : 0;
-    plan->waves_per_robot = rp ? rowpar_waves(b, B) : 0;
-    plan->segments = rp ? a.seg : 0;
-    plan->record_layout = a.rec_split ? NMPC_REC_SPLIT : NMPC_REC_WIDE;
-    plan->warm_tag = warm_tag_of(b, a);
+    // the plan schedule() launches from (a run_path launch marches its paths in the kernel)
+    const LaunchPlan p = plan_launch(b, B, mode == NMPC_PLAN_RUN_PATH, mode == NMPC_PLAN_SOLVE ? kModeSolve : kModeRun);
+    plan->kernel = p.waves ? 1 : 0;
+    plan->waves_per_robot = p.waves;
+    plan->segments = p.seg;
+    plan->record_layout = p.rec_split ? NMPC_REC_SPLIT : NMPC_REC_WIDE;
+    plan->warm_tag = p.warm_tag;
     plan->record_bytes = rec_footprint(b);
     return NMPC_OK;
 }
@@ -1128,25 +1040,12 @@ int fleet_sim(nmpc_batch* b, int B, float* path, float* s, float* pose, float* v
               const int* status, float* traj, int* traj_len, int advance, const nmpc_fleet_renew* renew, void* stream)
 {
     const TraceRange trace("nmpc_fleet_sim_step");
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (const int rc = check_batch(b, B)) return rc;
     if (!path || !s || !pose || !vel || !traj || (advance && !u0)) return set_err(NMPC_ERR_ARG, "NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
-    switch (b->prm.model) {
-    case NMPC_MODEL_DIFF2AMR:
-        e = launch_fleet_sim<Diff2>(b->kp, B, b->capacity, path, s, pose, vel, steer, u0, status, b->carried, traj,
-                                    traj_len, advance, renew, st);
-        break;
-    case NMPC_MODEL_OMNI4AMR:
-        e = launch_fleet_sim<Omni4>(b->kp, B, b->capacity, path, s, pose, vel, steer, u0, status, b->carried, traj,
-                                    traj_len, advance, renew, st);
-        break;
-    default:
-        e = launch_fleet_sim<Tric3>(b->kp, B, b->capacity, path, s, pose, vel, steer, u0, status, b->carried, traj,
-                                    traj_len, advance, renew, st);
-        break;
-    }
+    const hipError_t e = with_model(b->prm.model, [&](auto m) {
+        return launch_fleet_sim<decltype(m)>(b->kp, B, b->capacity, path, s, pose, vel, steer, u0, status, b->carried,
+                                             traj, traj_len, advance, renew, (hipStream_t)stream);
+    });
     return hip_err(e, "fleet_sim launch");
 }
 }  // namespace

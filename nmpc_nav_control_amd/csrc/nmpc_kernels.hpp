@@ -122,6 +122,11 @@ hipError_t launch_node_order(const int* key, const unsigned char* active, int B,
 // sorted order (hardest first) plus nhard[0] = min(#robots with key >= H, cap): the hybrid launch's split
 hipError_t launch_hybrid_order(const int* key, int B, int H, int cap, int* order, int* nhard, hipStream_t stream);
 #endif
+// the resident state of the first B robots as nmpc_batch_init_iterate leaves it (mode 0 create, 1 reset), warm flags
+// cleared; launch_forget_warm clears the warm flags alone, of the robots with mask[i] != 0 (nullptr: all)
+hipError_t launch_init_iterate(float* xbar, float* ubar, float* carried, unsigned char* warm, int B, int stride, int N,
+                               int nx, int nu, int nbx, int mode, hipStream_t stream);
+hipError_t launch_forget_warm(unsigned char* warm, const unsigned char* mask, int B, hipStream_t stream);
 hipError_t launch_path_discretize(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
                                   const double* nearest_u, double period, int num_poses, int holo, float* traj,
                                   double* traj64, hipStream_t stream);
@@ -130,6 +135,10 @@ hipError_t launch_path_discretize(int B, const nmpc_path_segment* segs, int seg_
 hipError_t launch_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
                                const float* pose, const double* lo, const double* hi, int holo, double* nearest_u,
                                double* near, double* err, hipStream_t stream);
+// the path-error check of nmpc_batch_follow_path on err [2][B]: off_path [B] (or nullptr) and the stop command in cmd
+// [3][B] (or nullptr) for the robots whose error reaches a threshold whose comparison is on (use_pos / use_ori)
+hipError_t launch_path_guard(int B, const double* err, double max_pos, double max_ori, int use_pos, int use_ori,
+                             unsigned char* off_path, float* cmd, hipStream_t stream);
 
 // The gate of a node tick (node_gate.hip): per robot the mode switch of NMPCNavControlROS::mainCycle up to the solve
 // decision. Device pointers, [field][B]; the nullable ones as in nmpc_batch_node_tick.
@@ -158,5 +167,10 @@ struct NodeGateArgs {
 };
 hipError_t launch_node_gate(const NodeGateArgs& g, hipStream_t stream);
 size_t node_gate_lds_bytes(int N);
+// after the tick's solve launch, for the robots with active[i] != 0: reset consumed, a failed solve (status != 0) to
+// NMPC_NODE_ERROR (remains, the queue's, to NaN); n_solved[0] = n_active[0]
+hipError_t launch_node_finish(int B, const unsigned char* active, const int* status, const int* n_active,
+                              unsigned char* mode, unsigned char* event, unsigned char* reset, int* n_solved,
+                              double* remains, hipStream_t stream);
 
 }  // namespace nmpc

@@ -318,7 +318,34 @@ inline int march_block(int N)
     return block;
 }
 
+// after a node tick's solve launch: a robot that solved has consumed its pending reset, and a failed solve sends it
+// to Error (NMPCNavControlROS.cpp:716-719); n_solved receives the active count
+__global__ void k_node_finish(int B, const unsigned char* active, const int* status, const int* n_active,
+                              unsigned char* mode, unsigned char* event, unsigned char* reset, int* n_solved,
+                              double* remains)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && n_solved) n_solved[0] = n_active[0];
+    if (i >= B || !active[i]) return;
+    if (reset) reset[i] = 0;
+    if (status[i] != 0) {
+        mode[i] = NMPC_NODE_ERROR;
+        if (event) event[i] = NMPC_NODE_EV_SOLVE_FAILED;
+        if (remains) remains[i] = __builtin_nan("");  // (node_tick_queue: no longer in FollowPath)
+    }
+}
+
 }  // namespace
+
+hipError_t launch_node_finish(int B, const unsigned char* active, const int* status, const int* n_active,
+                              unsigned char* mode, unsigned char* event, unsigned char* reset, int* n_solved,
+                              double* remains, hipStream_t stream)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_node_finish, dim3((B + kGateBlock - 1) / kGateBlock), dim3(kGateBlock), 0, stream, B, active,
+                       status, n_active, mode, event, reset, n_solved, remains);
+    return hipGetLastError();
+}
 
 size_t node_gate_lds_bytes(int N)
 {

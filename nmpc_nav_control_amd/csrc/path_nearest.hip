@@ -51,7 +51,29 @@ __global__ void __launch_bounds__(kNearBlock) k_path_nearest(int B, const nmpc_p
     }
 }
 
+// the path-error check of a FollowPath tick (NMPCNavControlROS.cpp:658-660): a robot whose position or orientation
+// error reaches its threshold is flagged and gets the stop command; use_pos / use_ori: the comparison is on
+__global__ void k_path_guard(int B, const double* err, double max_pos, double max_ori, int use_pos, int use_ori,
+                             unsigned char* off_path, float* cmd)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const bool off = (use_pos && err[i] >= max_pos) || (use_ori && err[(size_t)B + i] >= max_ori);
+    if (off_path) off_path[i] = off ? 1 : 0;
+    if (off && cmd)
+        for (int j = 0; j < 3; j++) cmd[(size_t)j * B + i] = 0.0f;
+}
+
 }  // namespace
+
+hipError_t launch_path_guard(int B, const double* err, double max_pos, double max_ori, int use_pos, int use_ori,
+                             unsigned char* off_path, float* cmd, hipStream_t stream)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_path_guard, dim3((B + 255) / 256), dim3(256), 0, stream, B, err, max_pos, max_ori, use_pos,
+                       use_ori, off_path, cmd);
+    return hipGetLastError();
+}
 
 hipError_t launch_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
                                const float* pose, const double* lo, const double* hi, int holo, double* nearest_u,

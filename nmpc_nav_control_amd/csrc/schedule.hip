@@ -154,7 +154,47 @@ __global__ __launch_bounds__(kOrderThreads) void k_node_order(const int* __restr
     for (int i = i0; i < i1; i++) order[cnt[bin_of(i)][t]++] = i;
 }
 
+// the resident state's elementwise kernels (nmpc_batch_init_iterate, nmpc_batch_forget_warm)
+__global__ void k_init_iterate(float* xbar, float* ubar, float* carried, unsigned char* warm, int B, int stride, int N,
+                               int nx, int nu, int nbx, int mode)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    warm[i] = 0;  // the next solve starts its IPM cold
+    for (int k = 0; k <= N; k++)
+        for (int j = 0; j < nx; j++)
+            xbar[((size_t)k * nx + j) * stride + i] = (mode == 0 && j == 2) ? 3.14159265358979323846f : 0.0f;
+    for (int k = 0; k < N; k++)
+        for (int j = 0; j < nu; j++) ubar[((size_t)k * nu + j) * stride + i] = 0.0f;
+    // create semantics start the wrapper's x0 vel-refs at zero (the member struct is value-initialised); a reset
+    // (reset_mpc -> {name}_acados_reset) leaves them, as the reference does and as the solve's reset mask does
+    if (mode == 0)
+        for (int j = 0; j < nbx; j++) carried[(size_t)j * stride + i] = 0.0f;
+}
+
+__global__ void k_forget_warm(unsigned char* warm, const unsigned char* mask, int B)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < B && (!mask || mask[i])) warm[i] = 0;
+}
+
 }  // namespace
+
+hipError_t launch_init_iterate(float* xbar, float* ubar, float* carried, unsigned char* warm, int B, int stride, int N,
+                               int nx, int nu, int nbx, int mode, hipStream_t stream)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_init_iterate, dim3((B + 255) / 256), dim3(256), 0, stream, xbar, ubar, carried, warm, B,
+                       stride, N, nx, nu, nbx, mode);
+    return hipGetLastError();
+}
+
+hipError_t launch_forget_warm(unsigned char* warm, const unsigned char* mask, int B, hipStream_t stream)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_forget_warm, dim3((B + 255) / 256), dim3(256), 0, stream, warm, mask, B);
+    return hipGetLastError();
+}
 
 hipError_t launch_node_order(const int* key, const unsigned char* active, int B, int sorted, int* order, int* n_active,
                              hipStream_t stream)

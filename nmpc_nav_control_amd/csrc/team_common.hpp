@@ -77,7 +77,7 @@ struct TeamRec {
     // registers for 35 % less traffic), so diff keeps the 64-B records
     // SPLIT_OK: the layout exists for the model (diff, tric); SPLIT: tric always takes it. For diff the host picks
     // per launch (KArgs::rec_split): wide records alone on the device (the metric: -1.2 % with split planes), split
-    // planes beside other resident fleets (mixed: 5.25 -> 5.76 M it/s; nmpc_batch.cpp rec_split_auto)
+    // planes beside other resident fleets (mixed: 5.25 -> 5.76 M it/s; nmpc_batch.cpp rec_layout_auto)
 #ifndef NMPC_REC_FULL
     static constexpr bool SPLIT_OK = L2 && !rec_quad_major_v(NV);
     static constexpr bool SPLIT = SPLIT_OK && M::ID == kTric;

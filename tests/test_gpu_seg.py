@@ -162,3 +162,39 @@ def test_plan_defaults(built):
     assert ht.plan(64) == ("rowpar", 4, 6)
     ho = BatchSolver("omni4", 40, 512, params=default_params("omni4", 40))
     assert ho.plan(256)[0] == "rowpar" and ho.plan(300)[0] == "team"  # 357 registers: one wave per SIMD
+
+
+def test_plan_is_what_the_launch_runs(built):
+    """nmpc_batch_plan_ex reports the plan the launch takes (one function, nmpc_batch.cpp plan_launch): on one diff
+    handle a `run` launch on fresh state at the sizes on either side of each of the plan's rules (four waves per robot
+    up to 256, two up to 1024, then the team kernel) leaves the plan's warm tag in the flag of every robot it solved,
+    under the handle's own record layout and under the split one, whose tag only the team kernel's launch carries.
+    run_path launches stay on the team kernel at every size. qp_warm_iter_max = 0 switches diff's "warm only after an
+    easy solve" rule off, so that every successful solve leaves its tag."""
+    from nmpc_nav_control_amd.scenario import make_fleet
+    N, cap = 20, 1025
+    prm = default_params("diff", N)
+    prm.qp_warm_iter_max = 0
+    h = BatchSolver("diff", N, cap, params=prm)
+    fl = make_fleet("diff", cap, seed=7)
+    pose, vel, path, s, carried = (t(fl[k]) for k in ("pose", "vel", "path", "s", "carried"))
+    traj = torch.zeros(N + 1, 3, cap, device=DEV)
+    tlen = torch.zeros(cap, dtype=torch.int32, device=DEV)
+    h.state()[2].copy_from(carried)
+    h.fleet_sim_step(path, s, pose, vel, None, None, None, traj, tlen, advance=False)
+    for layout in ("auto", "split"):
+        h.set_record_layout(layout)
+        for B, waves in ((1, 4), (256, 4), (257, 2), (1024, 2), (1025, 0)):
+            plan = h.plan_ex(B, "run")
+            assert plan["waves_per_robot"] == waves and plan["kernel"] == ("rowpar" if waves else "team"), (B, plan)
+            assert h.plan_ex(B, "run_path")["kernel"] == "team", B
+            h.init_iterate(mode=0)
+            h.state()[2].copy_from(carried)
+            status = torch.full((B,), -7, dtype=torch.int32, device=DEV)
+            h.run(pose[:, :B].contiguous(), vel[:, :B].contiguous(), traj[..., :B].contiguous(), traj_len=tlen[:B],
+                  status=status)
+            torch.cuda.synchronize()
+            warm = h.warm_state()[0].to_tensor()[0]
+            assert (status == 0).all(), (layout, B, status.unique())
+            assert (warm[:B] == plan["warm_tag"]).all() and (warm[B:] == 0).all(), (layout, B, warm.unique())
+        assert plan["warm_tag"] == (2 if layout == "split" else 1), (layout, plan)  # (B = 1025: the team kernel)
