@@ -472,8 +472,8 @@ void solve_group(std::vector<nmpc_capsule_impl*>& cs, std::vector<Packed>& ps, c
     const double tt = std::chrono::duration<double>(t2 - t0).count();
     const double tq = std::chrono::duration<double>(t2 - t1).count();
     if (std::getenv("NMPC_AMD_SHIM_TIMING"))
-        std::fprintf(stderr, "[nmpc_amd] solve_group n=%d engine %.3f pack %.3f h2d %.3f solve+d2h %.3f ms\n", n,
-                     std::chrono::duration<double>(ta - t0).count() * 1e3,
+        std::fprintf(stderr, "[nmpc_amd] solve_group n=%d staged=%d engine %.3f pack %.3f h2d %.3f solve+d2h %.3f ms\n",
+                     n, staged ? 1 : 0, std::chrono::duration<double>(ta - t0).count() * 1e3,
                      std::chrono::duration<double>(tb - ta).count() * 1e3,
                      std::chrono::duration<double>(t1 - tb).count() * 1e3, tq * 1e3);
     int rule_warm = 0, rule_wmax = 0, rule_imax = 0;

@@ -152,6 +152,25 @@ extern "C" int nmpc_debug_sstamps_rowpar(unsigned long long* host)
 #define RP_SSTAMP(i) ((void)0)
 #endif
 
+#ifdef NMPC_LAG_WAVE
+// checker build only (lib/chk_lag, tests/test_gpu_rowpar_handoff.py): one wave of every robot with inst % 3 == 1 --
+// wave NMPC_LAG_WAVE of a four-wave block, wave 0 (the factorisation's) of a two-wave block -- falls behind the rest of
+// its block before its first P0a round and at its entry to phase B in every IPM iteration, so that every wave that
+// takes its data through an LDS counter really has to wait for it. Timing only: the arithmetic is the product's, so a
+// result that differs from the product's is an ordering dependence. The lag is a fixed run of 16 s_sleep 127
+// (16 x 127 x 64 = about 130 k cycles; no loop on memory, no data-dependent bound), sized against the whole of P0a
+// (24 k cycles) and a phase-B segment (20.7 k mean, 33.5 k max: profiles/r06/stamps/rowpar_B1024_N40.txt): the other
+// waves are done with either well before the lagging wave starts. The spin loops' bound of 1 << 24 polls of at least
+// 64 cycles each is four orders of magnitude above it.
+#define RP_LAG()                                                                                                 \
+    do {                                                                                                         \
+        if (wave == (W == 4 ? (NMPC_LAG_WAVE) : 0) && inst % 3 == 1)                                             \
+            for (int lag_i = 0; lag_i < 16; lag_i++) __builtin_amdgcn_s_sleep(127);                              \
+    } while (0)
+#else
+#define RP_LAG() ((void)0)
+#endif
+
 namespace {
 
 template <int F0, int F1, int RS, bool QM>
@@ -347,9 +366,12 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     auto it_rd = [&](int k, int f) -> float { return it_lds[((size_t)k * IT::NF + f) * NV + rv]; };
     auto it_wr = [&](int k, int f, bool w) -> float* { return w ? it_lds + ((size_t)k * IT::NF + f) * NV + r : lpad; };
     // Four waves, segmented: wave 0 runs P0b's initial-iterate pass while waves 1-3 integrate the stages (P0a, rounds
-    // of 12 stages), taking each round as soon as its three waves have stored it: s_cnt counts the finished
-    // wave-rounds (an LDS word the block reductions leave unused). Otherwise every row integrates and P0b follows a
-    // block barrier. -DNMPC_P0_NO_OVERLAP keeps the barrier for A/B runs.
+    // of 12 stages), taking each round as soon as all three waves have stored it: each P0a wave counts its own
+    // finished rounds in p_cnt[8 w] (slot 6 of its row of s_red; the block reductions combine at most 6 values, slots
+    // 0-5), and round j is in LDS once every one of the three counts has reached j + 1. (A single count of
+    // wave-rounds would not do: it also reaches 3 (j + 1) when one wave is three rounds ahead of the others.)
+    // Otherwise every row integrates and P0b follows a block barrier. -DNMPC_P0_NO_OVERLAP keeps the barrier for
+    // A/B runs and the checker build lib/chk_noov.
 #if defined(NMPC_P0_SERIAL) || defined(NMPC_P0_NO_OVERLAP)
     constexpr bool kP0Ov = false;
 #else
@@ -359,24 +381,30 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     constexpr int PROWS = ROWS - 4 * PW;        // rows of P0a
     const int prow = q - 4 * PW;                // this row among them (wave 0: negative, unused)
     const int pnr = (N + 1 + PROWS - 1) / PROWS;  // rounds of P0a
-    unsigned int* const s_cnt = reinterpret_cast<unsigned int*>(s_red + 7);
+    unsigned int* const p_cnt = reinterpret_cast<unsigned int*>(s_red + 6);  // [8 w], waves w = 1 .. 3
     if constexpr (W >= 2 && SEG) {  // (and phase B's counts of finished factorisation stages, s_red[15], s_red[23])
         if (tid == 0) {
-            *s_cnt = 0u;
+            if constexpr (kP0Ov) p_cnt[8] = p_cnt[16] = p_cnt[24] = 0u;
             reinterpret_cast<unsigned int*>(s_red)[15] = 0u;
             if constexpr (W == 4) reinterpret_cast<unsigned int*>(s_red)[23] = 0u;
         }
         __syncthreads();
     }
-    // (wave 0, and the unwrap's wave) wait until the round holding stage k is in LDS; bounded, never a hang
-    unsigned int seen = 0;
+    // (wave 0, and the unwrap's wave) wait until the round holding stage k is in LDS: until the slowest of the three
+    // P0a waves has counted it; bounded, never a hang
+    unsigned int seen = 0;  // rounds every P0a wave had finished at the last look
     auto wait_stage = [&](int k) {
         if constexpr (kP0Ov) {
             const int kk = k <= N ? k : N;
-            const unsigned int need = (unsigned int)(W - 1) * (unsigned int)(kk / PROWS + 1);
+            const unsigned int need = (unsigned int)(kk / PROWS + 1);
             for (int g = 0; seen < need && g < (1 << 24); g++) {
-                seen = __builtin_amdgcn_readfirstlane(
-                    __hip_atomic_load(s_cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+                unsigned int c = __hip_atomic_load(p_cnt + 8, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+                for (int w = 2; w < W; w++) {
+                    const unsigned int cw = __hip_atomic_load(p_cnt + 8 * w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    c = cw < c ? cw : c;
+                }
+                seen = __builtin_amdgcn_readfirstlane(c);
                 if (seen < need) __builtin_amdgcn_s_sleep(1);
             }
         }
@@ -447,9 +475,11 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
                 // LDS completes in order per wave: waiting for this wave's LDS operations is the release (a
                 // workgroup-scope fence would also wait for the next round's global loads in flight)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if ((tid & 63) == 0) __hip_atomic_fetch_add(s_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if ((tid & 63) == 0)
+                    __hip_atomic_fetch_add(p_cnt + 8 * wave, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         };
+        RP_LAG();
         In ca, cb;
         ld(prow, ca);
         for (int j = 0;; j += 2) {
@@ -1026,6 +1056,7 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
             };
             // finished factorisation stages of factor wave w (waves 0-1), counted over the whole launch
             unsigned int* const b_cnt = reinterpret_cast<unsigned int*>(s_red + 15);  // [w * 8]
+            RP_LAG();
             if (4 * wave < Sg) {  // (wave-uniform) the wave holds a segment
                 auto kof = [&](int j) { return srow ? (q + 1) * Ls - j : N; };
                 auto bseg = [&](int j, float (&rc)[RS]) {

@@ -251,3 +251,57 @@ def test_capsule_infeasible_qp_has_no_early_exit(built):
     torch.cuda.synchronize()
     assert int(st[0]) == 4 and int(it[0]) < 30, (int(st[0]), int(it[0]))
     assert cap_iter > int(it[0]), (cap_iter, int(it[0]))
+
+
+def test_staged_capsule_equals_copied(built, tmp_path):
+    """One capsule on the row-parallel kernel is solved in one launch: the kernel copies its own I/O block from and to
+    host-mapped memory (acados_shim.cpp `staged`); NMPC_AMD_CAPSULE_STAGE=0 keeps the copy, the kernel and the copy
+    back. Both run the same solve on the same numbers, so tests/capsule_probe.py's closed loops (diff N = 80, tric
+    N = 20: short reference lists, a reset, a NaN robot pose, which the shim rejects before any launch, and a NaN
+    reference pose, whose solve fails in the launch; both keep the iterate) must agree in every bit of every tick's status, IPM count, residual, u0, command and iterate. The NMPC_AMD_SHIM_TIMING line of every solve
+    says which path it took: `staged` falls back silently when the host-mapped block or the row-parallel plan is
+    missing, and a comparison of the copied path with itself would prove nothing."""
+    import os
+    import re
+    import subprocess
+    import sys
+
+    import capsule_probe as cp
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    procs = {}
+    for name in ("staged", "copied"):
+        env = dict(os.environ, NMPC_AMD_SHIM_TIMING="1")
+        env.pop("NMPC_AMD_CAPSULE_STAGE", None)
+        env.pop("NMPC_AMD_LIB", None)
+        if name == "copied":
+            env["NMPC_AMD_CAPSULE_STAGE"] = "0"
+        procs[name] = subprocess.Popen([sys.executable, os.path.join(root, "tests", "capsule_probe.py"),
+                                        str(tmp_path / f"{name}.npz")], env=env, stdout=subprocess.PIPE,
+                                       stderr=subprocess.PIPE, text=True)
+    outs = {}
+    try:
+        for name, p in procs.items():
+            _, err = p.communicate(timeout=300)
+            assert p.returncode == 0, (name, err[-3000:])
+            flags = re.findall(r"solve_group n=1 staged=(\d)", err)
+            # (every tick but the one rejected before its launch)
+            assert len(flags) == len(cp.CASES) * (cp.TICKS - 1), (name, len(flags), err[-2000:])
+            assert set(flags) == {"1" if name == "staged" else "0"}, (name, flags)
+            outs[name] = np.load(str(tmp_path / f"{name}.npz"))
+    finally:
+        for p in procs.values():
+            if p.poll() is None:
+                p.kill()
+    a, b = outs["staged"], outs["copied"]
+    for model, _ in cp.CASES:
+        for tick in range(cp.TICKS):
+            for k in cp.FIELDS:
+                u, v = a[f"{model}__t{tick}__{k}"], b[f"{model}__t{tick}__{k}"]
+                assert u.shape == v.shape and u.tobytes() == v.tobytes(), (model, tick, k, u, v)
+            st = int(a[f"{model}__t{tick}__status"])
+            assert (st != 0) == (tick in cp.FAIL_TICKS), (model, tick, st)
+        # a failed tick kept the iterate, and the next tick solved from it
+        for t in cp.FAIL_TICKS:
+            for k in ("xs", "us"):
+                assert np.array_equal(a[f"{model}__t{t}__{k}"], a[f"{model}__t{t - 1}__{k}"]), (model, t, k)
+                assert np.isfinite(a[f"{model}__t{t + 1}__{k}"]).all(), (model, t, k)
