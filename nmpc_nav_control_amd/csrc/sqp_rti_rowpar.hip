@@ -21,6 +21,7 @@
 // One robot per block also makes every loop exit block-uniform (no lockstep teams).
 #include "nmpc_kernels.hpp"
 #include "team_common.hpp"
+#include "sqp_steps.hpp"
 
 namespace nmpc {
 
@@ -85,7 +86,7 @@ struct SegLayout {
 // region where it fits there (P0 is done with it before the first IPM iteration, behind a block barrier)
 template <class M>
 struct RowLds {
-    static constexpr int SF = 5 + M::NGV;
+    static constexpr int SF = StageLds<M>::SF;
     __host__ __device__ static constexpr size_t r4(size_t f) { return (f + 3) / 4 * 4; }
     __host__ __device__ static constexpr size_t stage_floats(int N) { return (size_t)(N + 1) * SF * 16; }
     __host__ __device__ static constexpr size_t pad_off(int N) { return (size_t)(N + 1) * (16 * SF + 3 + 16 + 3) + 32; }
@@ -240,22 +241,11 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     const int N = P.N;
     const size_t S = (size_t)a.stride;
     const size_t Bn = (size_t)a.B;
-    const bool lv = r < NV;
-    const bool is_u = r < NU;
-    const bool is_x = lv && !is_u;
-    const int xi = is_x ? r - NU : 0;
-    const int cx = is_x ? xcomp<M>(xi) : -1;
-    const bool has_b = is_u || cx >= 0;
-    const float sc = P.dt;
-    const float w_lane = is_u ? P.W[NX + r] : (is_x ? P.W[xi] : 0.0f);
-    const float h_stage = sc * w_lane;
-    float lo_b = 0.0f, hi_b = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NU; j++)
-        if (r == j) { lo_b = P.lbu[j]; hi_b = P.ubu[j]; }
-#pragma unroll
-    for (int c = 0; c < M::NBX; c++)
-        if (cx == c) { lo_b = P.lbx[c]; hi_b = P.ubx[c]; }
+    // this lane's roles, stage weight and box (sqp_steps.hpp)
+    const LaneCtx<M> lc = lane_ctx<M>(P, r);
+    const bool lv = lc.lv, is_u = lc.is_u, is_x = lc.is_x, has_b = lc.has_b;
+    const int xi = lc.xi;
+    const float sc = P.dt, w_lane = lc.w_lane, h_stage = lc.h_stage, lo_b = lc.lo_b, hi_b = lc.hi_b;
     constexpr int KS = 16 * RSS;  // floats per stage block (the team kernel's layout)
     const int NR = (N + 1 + ROWS - 1) / ROWS;  // rounds of the stage-parallel phases
     float* const rbase = a.scratch + (size_t)inst * (N + 1) * KS;
@@ -302,33 +292,14 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
 
     // ---- x0 -----------------------------------------------------------------------------------------------
     float x0[NX];
-    float pose_th = 0.0f;
-    if (mode == kModeRun) {
-        const float pose[3] = {a.pose[inst], a.pose[Bn + inst], a.pose[2 * Bn + inst]};
-        const float vel[3] = {a.vel[inst], a.vel[Bn + inst], a.vel[2 * Bn + inst]};
-        const float steer = a.steer ? a.steer[inst] : 0.0f;
-        x0[0] = pose[0];
-        x0[1] = pose[1];
-        x0[2] = pose[2];
-        pose_th = pose[2];
-        M::direct_kin(vel, steer, P, x0 + 3);
-#pragma unroll
-        for (int i = 0; i < M::NBX; i++) x0[M::idxbx(i)] = a.carried[(size_t)i * S + inst];
-    } else {
-#pragma unroll
-        for (int j = 0; j < NX; j++) x0[j] = a.x0[(size_t)j * Bn + inst];
-    }
-    float x0_lane = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NX; j++)
-        if (xi == j) x0_lane = x0[j];
-    float we_lane = 0.0f;
-    if (is_x) we_lane = (mode != kModeRun && a.We) ? a.We[(size_t)xi * Bn + inst] : P.We[xi];
+    const X0Lane xl = load_x0<M>(P, a, mode, inst, lc, x0);
+    const float pose_th = xl.pose_th, x0_lane = xl.x0_lane;
+    float we_lane = xl.we_lane;  // (run mode: + the terminal hack, before P0c)
 
     // ---- P0a: RK4 linearisation of stage k on row k mod 4 -> LDS [k][field][lane] -----------------------------
-    // fields: zbar, yref entry, warm multipliers (2), defect b_k, the NGV varying Jacobian rows; run mode also the
-    // stage's reference pose in my_traj
-    constexpr int SF = 5 + NGV;
+    // (StageLds, sqp_steps.hpp); run mode also the stage's reference pose in my_traj
+    using SL = StageLds<M>;
+    constexpr int SF = SL::SF;
     extern __shared__ float s_row[];
     float* const s_stg = s_row;
     float* const my_traj = s_row + (size_t)(N + 1) * SF * 16;
@@ -372,7 +343,7 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     // wave-rounds would not do: it also reaches 3 (j + 1) when one wave is three rounds ahead of the others.)
     // Otherwise every row integrates and P0b follows a block barrier. -DNMPC_P0_NO_OVERLAP keeps the barrier for
     // A/B runs and the checker build lib/chk_noov.
-#if defined(NMPC_P0_SERIAL) || defined(NMPC_P0_NO_OVERLAP)
+#ifdef NMPC_P0_NO_OVERLAP
     constexpr bool kP0Ov = false;
 #else
     constexpr bool kP0Ov = W == 4 && SEG;
@@ -443,31 +414,15 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
             const int k = j * PROWS + prow;
             const bool kv = k <= N;
             if (mode == kModeRun) *((r < 3 && kv) ? my_traj + k * 3 + r : lpad) = cur.tq;
-            float xn[NX], g[NX];
+            const P0In<M> in = p0_stage_inputs<M>(P, lc, r, k, N, cur.x, cur.u, cur.xnext);  // (rows past the end: k > N)
+            float* const st = kv ? s_stg + SL::at(k, r) : nullptr;
+            *(kv ? st + SL::ZBAR : lpad) = in.zb;
+            *(kv ? st + SL::YREF : lpad) = cur.y;
+            *(kv ? st + SL::LL : lpad) = cur.l.x;
+            *(kv ? st + SL::LU : lpad) = cur.l.y;
+            *(kv ? st + SL::DEFECT : lpad) = in.bk;
 #pragma unroll
-            for (int i = 0; i < NX; i++) { xn[i] = 0.0f; g[i] = 0.0f; }
-            float bk = 0.0f;
-            if (k < N) {  // (rows past the end: k > N)
-                rk4_column<M>(cur.x, cur.u, P, lv ? r : NU, xn, g);
-#pragma unroll
-                for (int i = 0; i < NX; i++)
-                    if (is_x && xi == i) bk = xn[i] - cur.xnext;
-            }
-            float zb = 0.0f;
-#pragma unroll
-            for (int j2 = 0; j2 < NU; j2++)
-                if (r == j2) zb = cur.u[j2];
-#pragma unroll
-            for (int j2 = 0; j2 < NX; j2++)
-                if (is_x && xi == j2) zb = cur.x[j2];
-            float* const st = kv ? s_stg + (size_t)k * SF * 16 + r : nullptr;
-            *(kv ? st : lpad) = zb;
-            *(kv ? st + 16 : lpad) = cur.y;
-            *(kv ? st + 32 : lpad) = cur.l.x;
-            *(kv ? st + 48 : lpad) = cur.l.y;
-            *(kv ? st + 64 : lpad) = bk;
-#pragma unroll
-            for (int i = 0; i < NGV; i++) *(kv ? st + (5 + i) * 16 : lpad) = g[i];
+            for (int i = 0; i < NGV; i++) *(kv ? st + SL::gv(i) : lpad) = in.g[i];
         };
         // (overlap: this wave's stores of the round are in LDS, then its count)
         auto signal = [&]() {
@@ -496,24 +451,12 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     // constant rows of [B A] (rows >= NGV) from stage 0 (every row, identically)
     float gcol[NX], grow[NV];
     {
-        float xb0[NX], ub0[NU], xn0[NX], g0[NX];
+        float xb0[NX], ub0[NU];
 #pragma unroll
         for (int j = 0; j < NX; j++) xb0[j] = XB(0, j);
 #pragma unroll
         for (int j = 0; j < NU; j++) ub0[j] = UBAR(0, j);
-        rk4_column<M>(xb0, ub0, P, lv ? r : NU, xn0, g0);
-#pragma unroll
-        for (int i = 0; i < NX; i++) gcol[i] = (lv && i >= NGV) ? g0[i] : 0.0f;
-        sfor<0, NV>([&](auto vc) {
-            constexpr int v = decltype(vc)::value;
-            float sv = 0.0f;
-#pragma unroll
-            for (int i = NGV; i < NX; i++) {
-                const float t = bc<v>(gcol[i]);
-                if (is_x && xi == i) sv = t;
-            }
-            grow[v] = sv;
-        });
+        const_rows<M>(P, lc, r, xb0, ub0, gcol, grow);
     }
     if constexpr (!kP0Ov) __syncthreads();  // the stage inputs of every row are in LDS
     RP_STAMP(1);
@@ -525,17 +468,16 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     // scalar branches per stage, 575 cycles per stage step at one robot; profiles/r06/ab/p0b_w4.txt)
     float* const s_dx = s_red + 32;                  // [N+1][16]
     float* const s_ref = s_dx + (size_t)(N + 1) * 16;  // [N+1][3]
-#ifndef NMPC_P0_SERIAL
     if (w0) {
         struct Stg {
             float b, g[NGV];
         };
         auto lds_ld = [&](int k, Stg& o) {
             const int kk = k <= N ? k : N;
-            const float* const st = s_stg + (size_t)kk * SF * 16 + r;
-            o.b = st[64];
+            const float* const st = s_stg + SL::at(kk, r);
+            o.b = st[SL::DEFECT];
 #pragma unroll
-            for (int i = 0; i < NGV; i++) o.g[i] = st[(5 + i) * 16];
+            for (int i = 0; i < NGV; i++) o.g[i] = st[SL::gv(i)];
         };
         // store dx_k, then dx_{k+1} (every LDS store unconditional; rows 1-3 of wave 0 write row 0's identical values)
         float dx = is_x ? x0_lane - XB(0, xi) : 0.0f;
@@ -574,22 +516,17 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     if (mode == kModeRun && wave == W - 1) {
         // (rows of the wave compute the same values; lanes 0-2 of each row store them, the rest store to a pad)
         wait_stage(N);  // (overlap: every round's reference poses)
-        float ref_x = 0.0f, ref_y = 0.0f, ref_t = pose_th;
+        RefUnwrap ref(pose_th);
         auto ld_t = [&](int k, float (&t)[3]) {
             const int kk = k <= N ? k : N;
 #pragma unroll
             for (int j = 0; j < 3; j++) t[j] = my_traj[kk * 3 + j];
         };
         auto uw = [&](int k, const float (&t)[3]) {
-            const bool in = k < len;
-            const float th = t[2], d = th - ref_t;
-            const float thu = (d > kPi) ? th - 2.0f * kPi : ((d < -kPi) ? th + 2.0f * kPi : th);
-            ref_x = in ? t[0] : ref_x;
-            ref_y = in ? t[1] : ref_y;
-            ref_t = in ? thu : ref_t;
-            float v = ref_t;
-            v = (r == 1) ? ref_y : v;
-            v = (r == 0) ? ref_x : v;
+            ref.step(k < len, t);
+            float v = ref.ref_t;
+            v = (r == 1) ? ref.ref_y : v;
+            v = (r == 0) ? ref.ref_x : v;
             *(r < 3 ? s_ref + k * 3 + r : lpad) = v;
         };
         float t0[3], t1[3], t2[3];
@@ -607,82 +544,22 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
             if (k + 2 == N) break;
         }
     }
-#else
-    // A/B only (-DNMPC_P0_SERIAL): round 5's single loop over both recursions on wave 0
-    if (w0) {
-        float dx = is_x ? x0_lane - XB(0, xi) : 0.0f;
-        float ref_x = 0.0f, ref_y = 0.0f, ref_t = pose_th;
-        struct Stg {
-            float b, g[NGV], t[3];
-        };
-        auto lds_ld = [&](int k, Stg& o) {
-            const int kk = k <= N ? k : N;
-            const float* const st = s_stg + (size_t)kk * SF * 16 + r;
-            o.b = st[64];
-#pragma unroll
-            for (int i = 0; i < NGV; i++) o.g[i] = st[(5 + i) * 16];
-#pragma unroll
-            for (int j = 0; j < 3; j++) o.t[j] = (mode == kModeRun) ? my_traj[kk * 3 + j] : 0.0f;
-        };
-        // one stage of the recursion (branch-free reference unwrap; every LDS store unconditional: lanes without
-        // an entry write their pad slot, rows 1-3 of wave 0 write row 0's identical values)
-        auto step = [&](int k, const Stg& cur) {
-            if (mode == kModeRun) {
-                const bool in = k < len;
-                const float th = cur.t[2], d = th - ref_t;
-                const float thu = (d > kPi) ? th - 2.0f * kPi : ((d < -kPi) ? th + 2.0f * kPi : th);
-                ref_x = in ? cur.t[0] : ref_x;
-                ref_y = in ? cur.t[1] : ref_y;
-                ref_t = in ? thu : ref_t;
-                *(r < 3 ? s_ref + k * 3 + r : lpad) = (r == 0) ? ref_x : ((r == 1) ? ref_y : ref_t);
-            }
-            s_dx[k * 16 + r] = dx;
-            if (k < N) {
-                const float dzd = is_x ? dx : 0.0f;
-                float nx_ = dot_v<NX, NU>(0.0f, dzd, grow);
-#pragma unroll
-                for (int i = 0; i < NGV; i++) {
-                    const float sr = row_sum16(lv ? cur.g[i] * dzd : 0.0f);
-                    if (xi == i) nx_ = sr;
-                }
-                dx = is_x ? nx_ + cur.b : 0.0f;
-            }
-        };
-        // three buffers used in turn, loads two stages ahead (no copies: a copy waits for the LDS read in flight)
-        Stg c0, c1, c2;
-        lds_ld(0, c0);
-        lds_ld(1, c1);
-        for (int k = 0;; k += 3) {
-            lds_ld(k + 2, c2);
-            step(k, c0);
-            if (k == N) break;
-            lds_ld(k + 3, c0);
-            step(k + 1, c1);
-            if (k + 1 == N) break;
-            lds_ld(k + 4, c1);
-            step(k + 2, c2);
-            if (k + 2 == N) break;
-        }
-    }
-#endif
     __syncthreads();
     RP_STAMP(2);
 
     // ---- P0c (stage-parallel): gradient, bounds, slacks, multipliers and the record of stage k on row k mod ROWS
-    if (mode == kModeRun && P.terminal_hack && is_x && xi < 3) {  // NMPCNavControlDiff.cpp:127-139
-        const bool eq = (s_ref[N * 3] == s_ref[(N - 1) * 3]) && (s_ref[N * 3 + 1] == s_ref[(N - 1) * 3 + 1]) &&
-                        (s_ref[N * 3 + 2] == s_ref[(N - 1) * 3 + 2]);
-        we_lane = (eq ? 100.0f : 1.0f) * w_lane;
-    }
+    if (mode == kModeRun && P.terminal_hack)
+        we_lane = terminal_weight(lc, we_lane, s_ref[N * 3] == s_ref[(N - 1) * 3] && s_ref[N * 3 + 1] == s_ref[(N - 1) * 3 + 1] &&
+                                                   s_ref[N * 3 + 2] == s_ref[(N - 1) * 3 + 2]);
     const float lam_thr = P.infeas_lam * fmaxf(1.0f, fmaxf(P.wmax, row_max16(is_x ? we_lane : 0.0f)) * 0.1f);
     float sum_c0 = 0.0f;
     for (int j = 0; j < NR; j++) {
         const int kr = j * ROWS + q;
         const bool kv = kr <= N;
         const int k = kv ? kr : N;
-        const float* const st = s_stg + (size_t)k * SF * 16 + r;
-        const float zbar = st[0];
-        const float yr = (mode == kModeRun) ? ((is_x && xi < 3) ? s_ref[k * 3 + xi] : 0.0f) : st[16];
+        const float* const st = s_stg + SL::at(k, r);
+        const float zbar = st[SL::ZBAR];
+        const float yr = (mode == kModeRun) ? ((is_x && xi < 3) ? s_ref[k * 3 + xi] : 0.0f) : st[SL::YREF];
         const float dxk = s_dx[k * 16 + r];
         float rec[RS];
 #pragma unroll
@@ -693,25 +570,16 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
         rec[R::GR] = valid ? w * (zbar - yr) : 0.0f;
         const float z = vx ? dxk : 0.0f;
         rec[R::Z] = z;
-        rec[R::TL] = kFar;
-        rec[R::TU] = kFar;
-        rec[R::LB] = -kFar;
-        rec[R::UB] = kFar;
-        if (valid && has_b) {
-            const float lb = lo_b - zbar, ubd = hi_b - zbar;
-            const float tl = fmaxf(z - lb, P.thr0), tu = fmaxf(ubd - z, P.thr0);
-            rec[R::LB] = lb;
-            rec[R::UB] = ubd;
-            rec[R::TL] = tl;
-            rec[R::TU] = tu;
-            const float ll0 = warm ? fmaxf(fminf(st[32], kWarmLambdaCap), P.warm_kappa / tl) : P.mu0 / tl;
-            const float lu0 = warm ? fmaxf(fminf(st[48], kWarmLambdaCap), P.warm_kappa / tu) : P.mu0 / tu;
-            rec[R::LL] = ll0;
-            rec[R::LU] = lu0;
-            sum_c0 += kv ? ll0 * tl + lu0 * tu : 0.0f;
-        }
+        const BoundStart b = bound_start(P, zbar, z, lo_b, hi_b, warm, make_float2(st[SL::LL], st[SL::LU]), valid && has_b);
+        rec[R::LB] = b.lb;
+        rec[R::UB] = b.ub;
+        rec[R::TL] = b.tl;
+        rec[R::TU] = b.tu;
+        rec[R::LL] = b.ll;
+        rec[R::LU] = b.lu;
+        sum_c0 += kv ? b.c0 : 0.0f;
 #pragma unroll
-        for (int i = 0; i < NGV; i++) rec[R::GV + i] = (k < N && lv) ? st[(5 + i) * 16] : 0.0f;
+        for (int i = 0; i < NGV; i++) rec[R::GV + i] = (k < N && lv) ? st[SL::gv(i)] : 0.0f;
         rec_store_range<0, RSS, RS, QM>(kv ? tbase_own + (size_t)k * KS : tdummy, rec);  // idle slots: own unused slot
     }
     {
@@ -731,20 +599,9 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     const int m = N * NU + N * M::NBX;
     const float inv_m2 = 0.5f / (float)m;
 
-    auto column = [&](const float (&rc)[RS], float (&Gc)[NX]) {
-#pragma unroll
-        for (int i = 0; i < NX; i++) Gc[i] = (i < NGV) ? rc[R::GV + (i < NGV ? i : 0)] : gcol[i];
-    };
-    auto dyn = [&](const float (&rc)[RS], float dzv) -> float {
-        float nx_ = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NGV; i++) {
-            const float s = row_sum16(lv ? rc[R::GV + i] * dzv : 0.0f);
-            if (xi == i) nx_ = s;
-        }
-        const float cr = dot_v<NX, NU>(0.0f, dzv, grow);
-        return (xi >= NGV) ? cr : nx_;
-    };
+    // (sqp_steps.hpp; the phases below call them through these names)
+    auto column = [&](const float (&rc)[RS], float (&Gc)[NX]) { stage_column<M, R::GV>(rc, gcol, Gc); };
+    auto dyn = [&](const float (&rc)[RS], float dzv) -> float { return stage_dyn<M, R::GV>(lc, rc, dzv, grow); };
     // the fields of one stage each serial pass reads: the Jacobian rows GV from the global record, the rest from LDS
     // (phase B: SIG, C0, GH; phase C: LR, LM; the adjoint: C0)
     auto ld_bfields = [&](int k, float (&v)[RS]) {
@@ -1685,22 +1542,7 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
             const int kk = k <= N ? k : N;
             return (w0 && is_x) ? &XB(kk, xi) : ((w0 && is_u && kk < N) ? &UBAR(kk, r) : tdummy);
         };
-        constexpr int EC = 8;
-        for (int k0 = 0; k0 <= N; k0 += EC) {
-            float zs[EC], vs[EC];
-#pragma unroll
-            for (int j = 0; j < EC; j++) {
-                const int kk = (k0 + j) <= N ? k0 + j : N;
-                zs[j] = tbase[(size_t)kk * KS + rec_off<RS, QM>(R::Z)];
-                vs[j] = *entry(k0 + j);
-            }
-#pragma unroll
-            for (int j = 0; j < EC; j++) {
-                const int k = k0 + j;
-                const float nv = (is_x && k == 0) ? x0_lane : vs[j] + zs[j];
-                if (k <= N) *entry(k) = nv;
-            }
-        }
+        sqp_full_step(N, is_x, x0_lane, entry, [&](int kk) { return tbase[(size_t)kk * KS + rec_off<RS, QM>(R::Z)]; });
         if (a.xtraj || a.utraj) {
             __threadfence_block();
             for (int k = 0; k <= N; k++) {
@@ -1710,6 +1552,9 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
         }
     }
     __threadfence_block();
+    // the output block of write_outputs (sqp_steps.hpp), written out here: with the call in its place the register
+    // allocation of the segmented phase B loop changed (two more copies and a wait in <Diff2, 4, true>), which this
+    // kernel's latency does not afford. A change of the output rule is made there and here.
     if (tid == 0) {
         float u0[NU];
 #pragma unroll

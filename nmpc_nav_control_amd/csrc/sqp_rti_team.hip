@@ -24,6 +24,7 @@
 // skip their loads and stores).
 #include "nmpc_kernels.hpp"
 #include "team_common.hpp"
+#include "sqp_steps.hpp"
 #include "path_march.hpp"
 
 namespace nmpc {
@@ -126,24 +127,11 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     const size_t S = (size_t)a.stride;  // resident state stride (capacity)
     const size_t Bn = (size_t)a.B;
     const int inst = a.order ? a.order[hoff + team] : team;  // difficulty-ordered placement (schedule.hip)
-    const bool lv = r < NV;
-    const bool is_u = r < NU;
-    const bool is_x = lv && !is_u;
-    const int xi = is_x ? r - NU : 0;
-    const int cx = is_x ? xcomp<M>(xi) : -1;
-    const bool has_b = is_u || cx >= 0;  // bounded slot: every input (idxbu = all), states on idxbx
-    const float sc = P.dt;
-    // this lane's stage weight, read once: indexed by the lane, the W entries are vector loads from the kernel
-    // arguments, and inside P0's loop each one waited on vmcnt(0), i.e. on the previous stage's record stores
-    const float w_lane = is_u ? P.W[NX + r] : (is_x ? P.W[xi] : 0.0f);
-    const float h_stage = sc * w_lane;
-    float lo_b = 0.0f, hi_b = 0.0f;
-#pragma unroll
-    for (int q = 0; q < NU; q++)
-        if (r == q) { lo_b = P.lbu[q]; hi_b = P.ubu[q]; }
-#pragma unroll
-    for (int c = 0; c < M::NBX; c++)
-        if (cx == c) { lo_b = P.lbx[c]; hi_b = P.ubx[c]; }
+    // this lane's roles, stage weight and box (sqp_steps.hpp)
+    const LaneCtx<M> lc = lane_ctx<M>(P, r);
+    const bool lv = lc.lv, is_u = lc.is_u, is_x = lc.is_x, has_b = lc.has_b;
+    const int xi = lc.xi, cx = lc.cx;
+    const float sc = P.dt, w_lane = lc.w_lane, h_stage = lc.h_stage, lo_b = lc.lo_b, hi_b = lc.hi_b;
     // this lane's record of stage k: tbase + k * KS
     // idle slots (r >= NV) alias slot 0's record: their (unpredicated) loads then read valid data and touch no
     // extra cache lines; they never store
@@ -222,38 +210,17 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 
     // ---- x0 (every lane keeps the full vector) ----------------------------------------------------------
     float x0[NX];
-    float pose_th = 0.0f;
-    if (mode == kModeRun) {
-        const float pose[3] = {a.pose[inst], a.pose[Bn + inst], a.pose[2 * Bn + inst]};
-        const float vel[3] = {a.vel[inst], a.vel[Bn + inst], a.vel[2 * Bn + inst]};
-        const float steer = a.steer ? a.steer[inst] : 0.0f;
-        x0[0] = pose[0];
-        x0[1] = pose[1];
-        x0[2] = pose[2];
-        pose_th = pose[2];
-        M::direct_kin(vel, steer, P, x0 + 3);
-#pragma unroll
-        for (int i = 0; i < M::NBX; i++) x0[M::idxbx(i)] = a.carried[(size_t)i * S + inst];
-    } else {
-#pragma unroll
-        for (int j = 0; j < NX; j++) x0[j] = a.x0[(size_t)j * Bn + inst];
-    }
-    float x0_lane = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NX; j++)
-        if (xi == j) x0_lane = x0[j];
-
-    // terminal weight of this lane's state (solve mode: caller's W_e; run mode: constructor W_e + diff hack)
-    float we_lane = 0.0f;
-    if (is_x) we_lane = (mode != kModeRun && a.We) ? a.We[(size_t)xi * Bn + inst] : P.We[xi];
+    const X0Lane xl = load_x0<M>(P, a, mode, inst, lc, x0);
+    const float pose_th = xl.pose_th, x0_lane = xl.x0_lane;
+    float we_lane = xl.we_lane;  // (run mode: + the terminal hack, P0's stage N)
 
     // ---- P0: linearisation (lane v: nominal step + column v), gradient, bounds, feasible initial iterate --
     // Split launches: the RK4 integrations and every global load of P0 do not depend on each other; only the
     // initial-iterate simulation (and the reference unwrap) is a recursion over the stages. The block's 16 rows
-    // (4 waves) take stages row, row + 16, ... and, after a block barrier, leave each lane's stage inputs in LDS ([k][field][lane], SF
-    // fields: zbar, yref entry, warm multipliers, defect b_k = xn_i - xbar_{k+1,i}, the NGV varying Jacobian
-    // rows) and run-mode reference poses in row 0's pose slice; row 0 then runs the serial pass from LDS only.
-    constexpr int SF = 5 + NGV;
+    // (4 waves) take stages row, row + 16, ... and, after a block barrier, leave each lane's stage inputs in LDS
+    // (StageLds, sqp_steps.hpp) and run-mode reference poses in row 0's pose slice; row 0 then runs the serial
+    // pass from LDS only.
+    using SL = StageLds<M>;
     if (a.split) {
         const int len_a = (mode == kModeRun) ? ((a.traj_len && !path) ? a.traj_len[inst] : N + 1) : 0;
         // a stage's global inputs, loaded one stage (of this row) ahead while the current one integrates
@@ -287,31 +254,15 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         for (int k = row; k <= N; k += 16) {
             ld(k + 16, nxt);
             if (mode == kModeRun && !path && r < 3) my_traj[k * 3 + r] = cur.tq;
-            float xn[NX], g[NX];
+            const P0In<M> in = p0_stage_inputs<M>(P, lc, r, k, N, cur.x, cur.u, cur.xnext);
+            float* const st = s_stg + SL::at(k, r);
+            st[SL::ZBAR] = in.zb;
+            st[SL::YREF] = cur.y;
+            st[SL::LL] = cur.l.x;
+            st[SL::LU] = cur.l.y;
+            st[SL::DEFECT] = in.bk;
 #pragma unroll
-            for (int i = 0; i < NX; i++) { xn[i] = 0.0f; g[i] = 0.0f; }
-            float bk = 0.0f;
-            if (k < N) {
-                rk4_column<M>(cur.x, cur.u, P, lv ? r : NU, xn, g);
-#pragma unroll
-                for (int i = 0; i < NX; i++)
-                    if (is_x && xi == i) bk = xn[i] - cur.xnext;
-            }
-            float zb = 0.0f;
-#pragma unroll
-            for (int j = 0; j < NU; j++)
-                if (r == j) zb = cur.u[j];
-#pragma unroll
-            for (int j = 0; j < NX; j++)
-                if (is_x && xi == j) zb = cur.x[j];
-            float* const st = s_stg + (size_t)k * SF * 16 + r;
-            st[0] = zb;
-            st[16] = cur.y;
-            st[32] = cur.l.x;
-            st[48] = cur.l.y;
-            st[64] = bk;
-#pragma unroll
-            for (int i = 0; i < NGV; i++) st[(5 + i) * 16] = g[i];
+            for (int i = 0; i < NGV; i++) st[SL::gv(i)] = in.g[i];
             cur = nxt;
         }
         __syncthreads();  // every row's stage inputs are in LDS
@@ -321,7 +272,8 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 #endif
     }
     const int len = (mode == kModeRun) ? ((a.traj_len && !path) ? a.traj_len[inst] : N + 1) : 0;
-    float ref_x = 0.0f, ref_y = 0.0f, ref_t = pose_th, prv_x = 0.0f, prv_y = 0.0f, prv_t = 0.0f;
+    RefUnwrap ref(pose_th);  // the stage reference (run mode), and stage N - 1's for the terminal hack
+    float prv_x = 0.0f, prv_y = 0.0f, prv_t = 0.0f;
     // Iterate rows are read two stages ahead (every lane of a team reads the same addresses: one request per
     // wave), the reference row likewise.
     auto load_row = [&](int k, float (&xr)[NX], float (&ur)[NU], float (&tr)[3]) {
@@ -345,22 +297,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     // constant rows of [B A] (rows >= NGV) from stage 0, before the sweep: lane v holds column v (gcol), lane
     // NU+xi holds row xi (grow), so the initial-iterate dynamics below need only NGV row sums
     float gcol[NX], grow[NV];
-    {
-        float xn0[NX], g0[NX];
-        rk4_column<M>(xb, ub, P, lv ? r : NU, xn0, g0);
-#pragma unroll
-        for (int i = 0; i < NX; i++) gcol[i] = (lv && i >= NGV) ? g0[i] : 0.0f;
-        sfor<0, NV>([&](auto vc) {
-            constexpr int v = decltype(vc)::value;
-            float sv = 0.0f;
-#pragma unroll
-            for (int i = NGV; i < NX; i++) {
-                const float t = bc<v>(gcol[i]);
-                if (is_x && xi == i) sv = t;
-            }
-            grow[v] = sv;
-        });
-    }
+    const_rows<M>(P, lc, r, xb, ub, gcol, grow);
     float dx = is_x ? x0_lane - XB(0, xi) : 0.0f;  // this lane's state delta at the current stage
     float sum_c0 = 0.0f;  // complementarity of the initial point (its mean sets the first SD target)
     // warm start: the previous multipliers (LL, LU) of the stage, prefetched one stage ahead
@@ -383,20 +320,13 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         // entries >= 3 of yref are left at zero
         float yr = yr_in;
         if (mode == kModeRun) {
-            // branch-free (selects): a divergent branch here (len is per team) made the compiler's waits at its
-            // join drain the whole memory counter, the stage's record stores included
-            const bool in = k < len;
-            const float th = trk[2], d = th - ref_t;
-            const float thu = (d > kPi) ? th - 2.0f * kPi : ((d < -kPi) ? th + 2.0f * kPi : th);
-            ref_x = in ? trk[0] : ref_x;
-            ref_y = in ? trk[1] : ref_y;
-            ref_t = in ? thu : ref_t;
-            if (k == N - 1) { prv_x = ref_x; prv_y = ref_y; prv_t = ref_t; }
+            ref.step(k < len, trk);
+            if (k == N - 1) { prv_x = ref.ref_x; prv_y = ref.ref_y; prv_t = ref.ref_t; }
             // (one select per value: the nested conditional compiled to lane-mask branches)
             float v = 0.0f;
-            v = (is_x && xi == 2) ? ref_t : v;
-            v = (is_x && xi == 1) ? ref_y : v;
-            v = (is_x && xi == 0) ? ref_x : v;
+            v = (is_x && xi == 2) ? ref.ref_t : v;
+            v = (is_x && xi == 1) ? ref.ref_y : v;
+            v = (is_x && xi == 0) ? ref.ref_x : v;
             yr = v;
         }
         float rec[RS];
@@ -408,45 +338,24 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         // condition of this body is a select: as lane-mask branches they cost P0 about 14 branch regions per stage
         float w = sc * w_lane;
         if (k == N) {  // (k is wave-uniform)
-            float wt = we_lane;
-            if (mode == kModeRun && P.terminal_hack) {  // NMPCNavControlDiff.cpp:127-139
-                const bool eq = (ref_x == prv_x) && (ref_y == prv_y) && (ref_t == prv_t);
-                const float wh = (eq ? 100.0f : 1.0f) * w_lane;
-                const bool hk = is_x && xi < 3;
-                wt = hk ? wh : wt;
-                we_lane = hk ? wh : we_lane;
-            }
-            w = vx ? wt : w;
+            if (mode == kModeRun && P.terminal_hack)
+                we_lane = terminal_weight(lc, we_lane, ref.ref_x == prv_x && ref.ref_y == prv_y && ref.ref_t == prv_t);
+            w = vx ? we_lane : w;
         }
         rec[R::GR] = valid ? w * (zbar - yr) : 0.0f;
         // iterate, bounds, slacks, multipliers
         const float z = vx ? dx : 0.0f;
         rec[R::Z] = z;
-        // slots without a bound (or outside their stage range) get a sentinel bound at +-kFar with slack kFar
-        // and zero multipliers: every bounded-variable expression of the sweeps then vanishes on them (r = 0,
-        // Sigma = 0, no step bound), so the sweeps need no per-lane branches
+        // (sentinels on the slots without a bound, or outside their stage range: bound_start, sqp_steps.hpp)
         {
-            const bool bd = valid && has_b;
-            const float lb = lo_b - zbar, ubd = hi_b - zbar;
-            const float tl = fmaxf(z - lb, P.thr0), tu = fmaxf(ubd - z, P.thr0);
-            // cold: t lambda = mu0; warm: the previous multipliers, floored at kappa / t
-            // (previous multipliers capped at kWarmLambdaCap: a feasible QP of this OCP ends with multipliers of
-            // the size of its weights, < 1e2; a runaway value from a struggling solve would start the IPM at a huge
-            // complementarity)
-            // (one division per slack: with one per branch of the warm flag, a per-team value, the compiler split
-            // the lanes around two division sequences)
-            const float num = warm ? P.warm_kappa : P.mu0;
-            const float ql = num / tl, qu = num / tu;
-            const float ll0 = warm ? fmaxf(fminf(lp.x, kWarmLambdaCap), ql) : ql;
-            const float lu0 = warm ? fmaxf(fminf(lp.y, kWarmLambdaCap), qu) : qu;
-            rec[R::LB] = bd ? lb : -kFar;
-            rec[R::UB] = bd ? ubd : kFar;
-            rec[R::TL] = bd ? tl : kFar;
-            rec[R::TU] = bd ? tu : kFar;
-            rec[R::LL] = bd ? ll0 : 0.0f;
-            rec[R::LU] = bd ? lu0 : 0.0f;
-            const float c0 = ll0 * tl + lu0 * tu;
-            sum_c0 += bd ? c0 : 0.0f;
+            const BoundStart b = bound_start(P, zbar, z, lo_b, hi_b, warm, lp, valid && has_b);
+            rec[R::LB] = b.lb;
+            rec[R::UB] = b.ub;
+            rec[R::TL] = b.tl;
+            rec[R::TU] = b.tu;
+            rec[R::LL] = b.ll;
+            rec[R::LU] = b.lu;
+            sum_c0 += b.c0;
         }
 #pragma unroll
         for (int i = 0; i < NGV; i++) rec[R::GV + i] = (k < N && lv) ? g[i] : 0.0f;
@@ -488,15 +397,18 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         // the stage inputs are read from LDS one stage ahead (each dependent LDS read costs a round trip of the
         // one wave that runs this pass)
         struct Stg {
-            float v[5], g[NGV], t[3];
+            float zb, y, ll, lu, b, g[NGV], t[3];
         };
         auto lds_ld = [&](int k, Stg& o) {
             const int kk = k <= N ? k : N;
-            const float* const st = s_stg + (size_t)kk * SF * 16 + r;
+            const float* const st = s_stg + SL::at(kk, r);
+            o.zb = st[SL::ZBAR];
+            o.y = st[SL::YREF];
+            o.ll = st[SL::LL];
+            o.lu = st[SL::LU];
+            o.b = st[SL::DEFECT];
 #pragma unroll
-            for (int f = 0; f < 5; f++) o.v[f] = st[f * 16];
-#pragma unroll
-            for (int i = 0; i < NGV; i++) o.g[i] = st[(5 + i) * 16];
+            for (int i = 0; i < NGV; i++) o.g[i] = st[SL::gv(i)];
 #pragma unroll
             for (int j = 0; j < 3; j++) o.t[j] = (mode == kModeRun) ? my_traj[kk * 3 + j] : 0.0f;
         };
@@ -507,7 +419,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
             float g[NX];
 #pragma unroll
             for (int i = 0; i < NX; i++) g[i] = (i < NGV && k < N) ? cur.g[i < NGV ? i : 0] : 0.0f;
-            p0_body(k, cur.v[0], cur.v[1], cur.t, make_float2(cur.v[2], cur.v[3]), g, cur.v[4]);
+            p0_body(k, cur.zb, cur.y, cur.t, make_float2(cur.ll, cur.lu), g, cur.b);
             cur = nxt;
         }
     } else {
@@ -618,22 +530,6 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     const float inv_m2 = 0.5f / (float)m;
     sum_c0 = row_sum16(lv ? sum_c0 : 0.0f);
 
-    // dx_{k+1} (lane NU+i) = sum_v G_k[i][v] dz_v: NGV row sums over the stored columns + the constant rows
-    auto dyn = [&](const float (&rc)[RS], float dzv) -> float {
-        float nxt = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NGV; i++) {
-            const float s = row_sum16(lv ? rc[R::GV + i] * dzv : 0.0f);
-            if (xi == i) nxt = s;
-        }
-        const float cr = dot_v<NX, NU>(0.0f, dzv, grow);
-        return (xi >= NGV) ? cr : nxt;
-    };
-    // column v of [B A] at a stage (rows < NGV from the record)
-    auto column = [&](const float (&rc)[RS], float (&Gc)[NX]) {
-#pragma unroll
-        for (int i = 0; i < NX; i++) Gc[i] = (i < NGV) ? rc[R::GV + (i < NGV ? i : 0)] : gcol[i];
-    };
     // Stage sweeps k = k0, k0 + dir, ..., k1 with the next stage's record (sweep2: the next two) in flight while
     // body(k, rec) runs. The loop is unrolled by the number of register buffers, which are used in turn (no
     // copies between them), and the loads are never predicated: a conditional load or a buffer copy would make
@@ -777,7 +673,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                                 : ll * rl * itl + ll - lu * rr * itu - lu;
             STAMPF(1);
             float Gc[NX];
-            column(rc, Gc);
+            stage_column<M, R::GV>(rc, gcol, Gc);
             // adjoint: c_v = sum_l G[l][v] pi_{k+1}[l]
             const float cpi = (k < N) ? dot_x<NX, NU>(0.0f, piv, Gc) : 0.0f;
             const float hz = ((k < N) ? h_stage : we_lane) * z;
@@ -1028,7 +924,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                         pvc = is_x ? ghat : 0.0f;
                     } else {
                         float Gc[NX];
-                        column(rc, Gc);
+                        stage_column<M, R::GV>(rc, gcol, Gc);
                         float y = dot_x<NX, NU>(ghat, pvc, Gc);
                         float my_lr = 0.0f;
                         sfor<0, NU>([&](auto jc) {
@@ -1122,7 +1018,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                     else *((st && !SPL) ? tbase + (size_t)k * KS + (!corr ? rec_off<RS, QM>(R::DZA) : rec_off<RS, QM>(R::DZ))
                               : tdummy) = dz;  // (split records: single-direction only, DZ in the plane)
                 }
-                if (k < N) dxs = dyn(rc, valid ? dz : 0.0f);
+                if (k < N) dxs = stage_dyn<M, R::GV>(lc, rc, valid ? dz : 0.0f, grow);
             });
             };
             // one compiled body per pass kind: same-box A/B diff metric 1.553 -> 1.526 ms, tric 4.382 -> 4.363 ms
@@ -1159,9 +1055,6 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 
     // ---- full SQP step + outputs ----------------------------------------------------------------------
     if (status == 0) {
-        // one unconditional load of z and of the iterate entry, one store per lane and stage (lanes without an
-        // entry -- idle slots, u at stage N -- read and write the dummy record): under lane masks every wait in
-        // this loop was a vmcnt(0), one memory round trip per stage
         // this lane's entry of stage k (clamped: stages past N repeat stage N's, read-only below)
         // (both candidate addresses computed for every lane, then selected: as a pointer choice per lane class the
         // compiler branched around each address computation, two lane-mask regions per stage)
@@ -1171,22 +1064,9 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
             float* const pu = &UBAR(kk < N ? kk : N - 1, is_u ? r : 0);
             return is_x ? px : ((is_u && kk < N) ? pu : tdummy);
         };
-        constexpr int EC = 8;  // stages per batch: EC loads of each kind in flight, then EC stores
-        for (int k0 = 0; k0 <= N; k0 += EC) {
-            float zs[EC], vs[EC];
-#pragma unroll
-            for (int j = 0; j < EC; j++) {
-                const int kk = (k0 + j) <= N ? k0 + j : N;
-                zs[j] = SPL ? pc0[(size_t)kk * R::CS + R::Z] : tbase[(size_t)kk * KS + rec_off<RS, QM>(R::Z)];
-                vs[j] = *entry(k0 + j);
-            }
-#pragma unroll
-            for (int j = 0; j < EC; j++) {
-                const int k = k0 + j;
-                const float nv = (is_x && k == 0) ? x0_lane : vs[j] + zs[j];
-                if (k <= N) *entry(k) = nv;
-            }
-        }
+        sqp_full_step(N, is_x, x0_lane, entry, [&](int kk) {
+            return SPL ? pc0[(size_t)kk * R::CS + R::Z] : tbase[(size_t)kk * KS + rec_off<RS, QM>(R::Z)];
+        });
         if (a.xtraj || a.utraj) {
             __threadfence_block();
             for (int k = 0; k <= N; k++) {
@@ -1196,48 +1076,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         }
     }
     __threadfence_block();
-    if (r == 0) {
-        float u0[NU];
-#pragma unroll
-        for (int j = 0; j < NU; j++) {
-            u0[j] = UBAR(0, j);
-            if (a.u0) a.u0[(size_t)j * Bn + inst] = u0[j];
-        }
-        if (a.x1) {
-#pragma unroll
-            for (int j = 0; j < NX; j++) a.x1[(size_t)j * Bn + inst] = XB(1, j);
-        }
-        if (a.status) a.status[inst] = status;
-        if (a.qp_iter) a.qp_iter[inst] = it_done;
-        if (a.iter_key) a.iter_key[inst] = it_done;
-        // warm-start the next solve only from a solve that converged (not from one that ran to qp_iter_max)
-        // and only from an easy one (P.warm_iter_max, 12 by default: warm multipliers lengthen the hard QPs)
-        if (a.warm)
-            a.warm[inst] = (P.warm && status == 0 && it_done < P.iter_max && it_done <= P.warm_iter_max) ? a.warm_tag : 0;
-        if (a.qp_res) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) a.qp_res[(size_t)j * Bn + inst] = exit_res[j];
-        }
-        if (mode == kModeRun && status == 0) {
-            float rr[M::NBX], cmd[3];
-#pragma unroll
-            for (int i = 0; i < M::NBX; i++) {
-                rr[i] = x0[M::idxbx(i)] + u0[i] * P.dt_ctrl;
-                a.carried[(size_t)i * S + inst] = rr[i];
-            }
-            M::inverse_kin(rr, P, cmd);
-            if (a.cmd) {
-#pragma unroll
-                for (int j = 0; j < 3; j++) a.cmd[(size_t)j * Bn + inst] = cmd[j];
-            }
-        } else if (mode == kModeRun && a.cmd) {
-            // failed solve: the reference throws (processAcadosStatus, NMPCNavControl.cpp:14-23) and the node
-            // publishes a stop command (executeNMPC catch -> Status::Error, NMPCNavControlROS.cpp:716-719); the
-            // carried refs and the iterate stay as they were
-#pragma unroll
-            for (int j = 0; j < 3; j++) a.cmd[(size_t)j * Bn + inst] = 0.0f;
-        }
-    }
+    if (r == 0) write_outputs<M>(P, a, mode, inst, status, it_done, exit_res, x0);
 #undef XB
 #undef UBAR
 }
@@ -1250,7 +1089,7 @@ hipError_t launch_sqp_rti_team(const KParams& P, const KArgs& a, int mode, hipSt
     if (a.B <= 0) return hipSuccess;
     // split launches: one robot per 256-lane block, P0's stage inputs in LDS (41 KB for diff at N = 80); a
     // horizon whose inputs do not fit runs unsplit
-    const size_t stg = (size_t)(P.N + 1) * 16 * (5 + M::NGV) * sizeof(float);
+    const size_t stg = (size_t)(P.N + 1) * 16 * StageLds<M>::SF * sizeof(float);
     const size_t split_lds = stg + (mode == kModeRun ? (sizeof(double) + 3 * sizeof(float)) * (size_t)(P.N + 1) : 0);
     KArgs as = a;
     if (as.split && split_lds > 65536) as.split = 0;

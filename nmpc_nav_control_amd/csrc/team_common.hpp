@@ -284,12 +284,16 @@ __device__ __forceinline__ void chol_split_f32(float (&Lr)[M::NX + M::NU], float
 // entries broadcast to every lane), leaving the Schur complement in the state block. Both pivots come from the
 // block up front -- d0 = M00, d1 = M11 - M10^2 / M00 = det / M00 with det = M00 M11 - M10^2, so
 // 1 / sqrt(d1) = sqrt(M00) / sqrt(det) = (M00 / sqrt(M00)) rsq(det) -- and their two rsq + Newton chains run side by
-// side instead of one after the other (the second waited for the first column's update). fail: a pivot <= 0.
+// side instead of one after the other (the second waited for the first column's update). fail: a pivot <= 0, or a
+// block that is not finite: a barrier weight lambda / t that overflowed fp32 (an infeasible QP's slack at 1e-36) makes
+// M00 and det +inf, both "> 0", and the factor NaN one iteration later (status 1 where the sequential pivots of the
+// other models and of the row-parallel kernel, whose second pivot is then NaN, report the breakdown: status 4;
+// tests/test_gpu_split.py test_failure_outputs_agree_across_kernel_forms).
 template <int NX>
 __device__ __forceinline__ void chol_input_2(double (&Lr)[NX + 2], double m00, double m11, double m10, int r, bool& fail)
 {
     const double det = __builtin_fma(m00, m11, -(m10 * m10));
-    if (!(m00 > 0.0) || !(det > 0.0)) fail = true;
+    if (!(m00 > 0.0) || !(det > 0.0) || !(det < __builtin_huge_val())) fail = true;
     const double rd0 = drsq(fmax(m00, 1e-300));
     const double rq = drsq(fmax(det, 1e-300));
     const double rd1 = (m00 * rd0) * rq;

@@ -247,3 +247,90 @@ def test_constant_rows_per_launch(built, tmp_path, model):
     dx = float(np.abs(a["xtraj"] - b["xtraj"]).max())
     print(f"{model}: column form vs row form: u {du:.2e} x {dx:.2e}")
     assert du <= 3e-4 and dx <= 3e-4, (du, dx)
+
+
+# ---- the failure exits and the output block, one body for every kernel form (csrc/sqp_steps.hpp) --------------------
+# (form name, robots, creation overrides, what nmpc_batch_plan_ex must report for it)
+FAIL_FORMS = [("team", 3, dict(NMPC_AMD_ROWPAR_MAX=0, NMPC_AMD_SPLIT_MAX=0), dict(kernel="team")),
+              ("team_split", 3, dict(NMPC_AMD_ROWPAR_MAX=0), dict(kernel="team")),
+              ("rowpar_serial", 3, dict(NMPC_AMD_SEG=0), dict(kernel="rowpar", segments=0)),
+              ("rowpar_seg_w4", 3, dict(), dict(kernel="rowpar", waves_per_robot=4)),
+              ("rowpar_seg_w2", 257, dict(), dict(kernel="rowpar", waves_per_robot=2))]
+
+
+@pytest.mark.parametrize("model", ["diff", "omni4", "tric"])
+def test_failure_outputs_agree_across_kernel_forms(built, monkeypatch, model):
+    """The NaN exit (status 1, no iteration), the infeasibility exit (status 4, well before qp_iter_max), the stop
+    command and the kept iterate / carried refs of a failed robot, and clean robots untouched by failed neighbours,
+    in every form of the two solve kernels: team, team split launch, row-parallel with serial phases, segmented on
+    four waves and (diff, tric: omni4 takes the team kernel at 257 robots) segmented on two waves. Run mode, N = 8:
+    three clean ticks, then robot 0 gets a NaN pose and robot 1 a carried vel-ref of 50 m/s. The fp64 oracle
+    (rule="batched") gives status [1, 4, 0] after 0, 14-15 and 6 iterations of at most 50 on these inputs for every
+    model, so a count at the cap means the exit did not fire.
+
+    Measured (MI355X): diff [1, 4, 0] after 0 / 16 / 7 iterations, omni4 after 0 / 19 / 6, tric after 0 / 19 / 5, in
+    every form. (tric's team forms used to end in status 1 at iteration 20: the infeasible robot's barrier weight
+    overflows fp32 at iteration 19, and chol_input_2 took the infinite pivots for positive ones.)"""
+    N = 8
+    ref = None
+    for name, B, env, want in FAIL_FORMS:
+        if name == "rowpar_seg_w2" and model == "omni4":
+            continue
+        h = handle(monkeypatch, model, N, B, **env)
+        plan = h.plan_ex(B, "run")
+        assert all(plan[k] == v for k, v in want.items()), (name, plan)
+        if name.startswith("rowpar_seg"):
+            assert plan["segments"] > 0, (name, plan)
+        cap = h.params.qp_iter_max
+        pose = np.tile(np.array([[0.0], [0.0], [0.2]]), (1, B))
+        traj = np.zeros((N + 1, 3, B))
+        traj[:, 0, :] = np.linspace(0.0, 0.2, N + 1)[:, None]
+        traj[:, 1, :] = 0.05
+        traj[:, 2, :] = 0.3
+        P, V, T = t(pose), t(np.zeros((3, B))), t(traj)
+
+        def tick(p):
+            o_ = dict(u0=torch.zeros(h.nu, B, device=DEV), cmd=torch.full((3, B), 7.0, device=DEV),
+                      status=torch.full((B,), -7, dtype=torch.int32, device=DEV),
+                      qp_iter=torch.full((B,), -7, dtype=torch.int32, device=DEV))
+            h.run(p, V, T, cmd=o_["cmd"], u0=o_["u0"], status=o_["status"], qp_iter=o_["qp_iter"])
+            torch.cuda.synchronize()
+            return o_
+
+        for _ in range(3):
+            assert (tick(P)["status"] == 0).all(), name
+        saved = h.save_state()
+        clean = tick(P)
+        clean_state = [v.to_tensor() for v in h.state()]
+        h.restore_state(saved)
+        P2 = P.clone()
+        P2[0, 0] = float("nan")
+        cr = h.state()[2].to_tensor()
+        cr[0, 1] = 50.0
+        h.state()[2].copy_from(cr)
+        before = [v.to_tensor() for v in h.state()]
+        inj = tick(P2)
+        after = [v.to_tensor() for v in h.state()]
+        st, it = inj["status"].cpu().numpy(), inj["qp_iter"].cpu().numpy()
+        print(f"{model} {name}: status {st[:3]} qp_iter {it[:3]} (cap {cap})")
+        assert st[0] == 1 and st[1] == 4 and (st[2:] == 0).all(), (name, st[:4])
+        assert it[0] == 0 and 0 < it[1] < cap, (name, it[:3], cap)
+        # failed robots: the stop command, iterate and carried refs kept bit for bit
+        assert (inj["cmd"][:, :2] == 0).all(), name
+        for b_, a_ in zip(before, after):
+            assert torch.equal(b_[:, :2], a_[:, :2]), name
+        # clean robots: the same tick without the injections, bit for bit
+        for k in ("u0", "cmd", "status", "qp_iter"):
+            assert torch.equal(inj[k][..., 2:], clean[k][..., 2:]), (name, k)
+        for c_, a_ in zip(clean_state, after):
+            assert torch.equal(c_[:, 2:B], a_[:, 2:B]), name
+        # across the forms: the same robots 0-2 everywhere
+        cur = dict(status=inj["status"][:3].clone(), cmd=inj["cmd"][:, :2].clone(), u0=inj["u0"][:, :3].clone(),
+                   it0=int(it[0]))
+        if ref is None:
+            ref = cur
+        else:
+            assert torch.equal(cur["status"], ref["status"]) and torch.equal(cur["cmd"], ref["cmd"]), name
+            assert cur["it0"] == ref["it0"], name
+            assert close(cur["u0"], ref["u0"]) <= TOL_RP, (name, close(cur["u0"], ref["u0"]))
+        h.close()

@@ -1,7 +1,7 @@
 """Memory-counter waits in the gfx950 ISA of the solve kernel, per loop (a development check for the sweep loops).
 
-usage: python tools/isa_waits.py [--kernel Diff2ELb0ELb1ELi1] [--flags "-DFOO"] [--all]
-Compiles csrc/sqp_rti_team.hip to device assembly with the product flags (+ --flags), takes one kernel
+usage: python tools/isa_waits.py [--src sqp_rti_rowpar.hip] [--kernel Diff2ELb0ELb1ELi1] [--flags "-DFOO"] [--all]
+Compiles a solve kernel's file (--src, by default csrc/sqp_rti_team.hip) to device assembly with the product flags (+ --flags), takes one kernel
 instantiation and prints, for every loop, its header label, depth, instruction count, the number of fp64 DPP
 FMAs (the P1 factorisation loop is the one with ~120) and every s_waitcnt vmcnt in it with its line."""
 import argparse
@@ -16,9 +16,9 @@ FLAGS = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -fno-mat
          "-fno-slp-vectorize -mllvm -amdgpu-sched-strategy=max-ilp --cuda-device-only -S").split()
 
 
-def compile_asm(extra, out):
+def compile_asm(src, extra, out):
     cmd = ["/opt/rocm/bin/hipcc", *FLAGS, f"-I{ROOT}/include", f"-I{CSRC}", *extra,
-           os.path.join(CSRC, "sqp_rti_team.hip"), "-o", out]
+           os.path.join(CSRC, src), "-o", out]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 
 
@@ -52,13 +52,14 @@ def loops(lines):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", default="Diff2ELb0ELb1ELi1")  # diff, not dense, single-direction, run mode
+    ap.add_argument("--src", default="sqp_rti_team.hip", help="the kernel's file in csrc/")
     ap.add_argument("--flags", default="")
     ap.add_argument("--all", action="store_true", help="every loop, not only those with vmcnt waits")
     ap.add_argument("--asm", default="/tmp/isa_waits.s")
     ap.add_argument("--no-compile", action="store_true", help="analyse an existing --asm file")
     a = ap.parse_args()
     if not a.no_compile:
-        compile_asm(a.flags.split(), a.asm)
+        compile_asm(a.src, a.flags.split(), a.asm)
     lines = kernel_lines(a.asm, a.kernel)
     with open(a.asm + ".kernel.s", "w") as fh:  # the kernel alone; the printed line numbers index this file
         fh.write("\n".join(lines))
