@@ -95,7 +95,8 @@ int nmpc_model_params_set_limits(nmpc_model_params* prm, double v_max, double a_
  * initialised with {name}_acados_create semantics (x = [0,0,pi,0,...], u = 0) and carried refs = 0. */
 int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** out);
 int nmpc_batch_destroy(nmpc_batch* b);
-/* Replace weights / bounds / parameters / QP options (model and N must not change). */
+/* Replace weights / bounds / parameters / QP options (model and N must not change). While the per-robot table is
+ * on (nmpc_batch_set_robot_params below), lbx, ubx, lbu, ubu, W and W_e do not reach a launch. */
 int nmpc_batch_set_params(nmpc_batch* b, const nmpc_model_params* prm);
 int nmpc_batch_get_params(const nmpc_batch* b, nmpc_model_params* prm);
 /* Re-initialise instances [0, B): mode 0 = create semantics (x = [0,0,pi,0,...], u = 0, carried ref states 0);
@@ -365,6 +366,63 @@ int nmpc_batch_forget_warm(nmpc_batch* b, int B, const unsigned char* mask, void
 #define NMPC_WARM_TAG_SPLIT 2    /* the team kernel's split core / bound planes */
 #define NMPC_WARM_TAG_MEHROTRA 3 /* the Mehrotra rule's field order (NMPC_IPM_MEHROTRA) */
 int nmpc_batch_warm_state(nmpc_batch* b, unsigned char** warm, float** scratch, size_t* scratch_bytes);
+
+/* Per-robot bounds and weights. A handle has one nmpc_model_params; a fleet of one geometry still has loaded and
+ * empty vehicles, zones with their own speed limits and aisles that want a heavier heading weight (the reference runs
+ * one node per robot, each with its own yaml values, NMPCNavControlROS.cpp:96-110,164-176,234-259). The handle
+ * therefore owns a device table [rows][capacity], fp32, instance-minor like the carried refs, with the rows
+ *     lbx[NBX] ubx[NBX] lbu[NBU] ubu[NBU] W[NY] W_e[NX]
+ * in this order (diff 24 rows, omni4 42, tric 24). It is allocated by the first writer call below and starts with the
+ * handle's own parameters in every column (the fp32 values the kernels take from nmpc_model_params). While the table
+ * is on, every launch of the handle -- nmpc_batch_solve, _solve_iterate, _run, _run_path, _follow_path and both node
+ * ticks -- takes each robot's bounds and weights from the robot's column; while it is off (never written, or after
+ * nmpc_batch_clear_robot_params) every launch computes exactly what it computed without this interface.
+ * Each writer is one small launch on `stream`, with no host synchronisation and no host-side validation (the values
+ * are device data): a zone change for some robots costs one enqueue before the next tick.
+ * Rules:
+ *   - While the table is on, the six fields lbx, ubx, lbu, ubu, W and W_e of nmpc_batch_set_params do not reach a
+ *     launch (they are what a table allocated or cleared later starts from). The QP options, p, dt, dt_ctrl,
+ *     terminal_hack and tric_sin_bug still do.
+ *   - In nmpc_batch_solve / _solve_iterate a caller's We argument still wins over the table's W_e rows. Run mode's
+ *     terminal hack uses the robot's own stage weights, and the early infeasibility exit (qp_infeas_lambda) scales
+ *     with the robot's own largest stage or terminal weight.
+ *   - A robot's warm flag is left alone when its rows change: warm multipliers are clamped at the start of the
+ *     next solve (max(min(lambda, cap), kappa / t)), which covers multipliers that went stale with the old box.
+ *   - A NaN bound fails that robot alone, with status 1, as a NaN input does. A NaN weight does the same.
+ *   - lb > ub, and a box that the robot's carried reference state cannot reach within one stage, give that robot
+ *     a nonzero status through the solver's existing exits (status 4: infeasible QP or iteration limit); no other
+ *     robot is affected, and the robot keeps its iterate and carried refs and gets a stop command, as after any
+ *     failed solve. The input weights R must stay > 0, as nmpc_batch_create requires of the handle's.
+ *   - Two scopes stay with the handle: the model parameters p (b, tau_v, ...), which the kernels take as uniform
+ *     operands (the constant rows of the stage Jacobian are shared by the robots of a wave), and anything that
+ *     varies along the horizon (one W and one box per robot, for every stage).
+ * Argument errors (NMPC_ERR_ARG): B out of range, rp NULL, every field NULL (nmpc_batch_set_robot_limits: every
+ * array NULL), a NULL handle. */
+typedef struct nmpc_robot_params {
+    const float* lbx; /* [NBX][B] device, or NULL: those rows stay as they are */
+    const float* ubx; /* [NBX][B] */
+    const float* lbu; /* [NBU][B] */
+    const float* ubu; /* [NBU][B] */
+    const float* W;   /* [NY][B] */
+    const float* W_e; /* [NX][B] */
+} nmpc_robot_params;
+/* Write the rows of the non-NULL fields for robots [0, B) where mask[i] != 0 (mask [B] device, NULL: all). */
+int nmpc_batch_set_robot_params(nmpc_batch* b, int B, const nmpc_robot_params* rp, const unsigned char* mask,
+                                void* stream);
+/* The batched nmpc_model_params_set_limits, with the same mapping: ref states in [-v_max, v_max] (tric: v_ref only,
+ * alpha_ref in [alpha_min, alpha_max]), inputs in [-a_max, a_max] (tric: dv_ref only, dalpha_ref in [-dalpha_max,
+ * dalpha_max]). Each argument is a device array [B] or NULL (those rows stay); the three steering arrays are read
+ * for tric only. mask as above. */
+int nmpc_batch_set_robot_limits(nmpc_batch* b, int B, const float* v_max, const float* a_max, const float* alpha_min,
+                                const float* alpha_max, const float* dalpha_max, const unsigned char* mask,
+                                void* stream);
+/* The table's device view for checkpoints: *table [rows][stride] (stride = capacity), or NULL while the table is
+ * off. Each output may be NULL. With nmpc_batch_state and nmpc_batch_warm_state this is everything a solve reads
+ * from the handle. */
+int nmpc_batch_robot_params(nmpc_batch* b, float** table, int* rows, int* stride);
+/* Turn the table off: launches use the handle's parameters again. The next writer call starts a fresh table from the
+ * handle's parameters. (Host-side switch: it applies to the launches enqueued after it.) */
+int nmpc_batch_clear_robot_params(nmpc_batch* b);
 
 /* Record layout of the team kernel's single-direction scratch records, a per-handle choice fixed at create time
  * and changed only by this call (never by other handles):

@@ -71,6 +71,12 @@ class PathQueueStruct(ctypes.Structure):
                 ("remains", c_void_p)]
 
 
+class RobotParamsStruct(ctypes.Structure):
+    """Mirror of nmpc_robot_params (include/nmpc_amd/nmpc_batch.h): device pointers [n][B], None = rows untouched."""
+    _fields_ = [("lbx", c_void_p), ("ubx", c_void_p), ("lbu", c_void_p), ("ubu", c_void_p), ("W", c_void_p),
+                ("W_e", c_void_p)]
+
+
 # NMPC_NODE_* (a robot's state in the node's state machine) and NMPC_NODE_EV_* (what the tick did for it)
 NODE_IDLE, NODE_GOTO_POSE, NODE_FOLLOW_PATH, NODE_BREAK, NODE_ERROR = 0, 1, 2, 3, 4
 (NODE_EV_NONE, NODE_EV_SOLVED, NODE_EV_ARRIVED, NODE_EV_GOAL_TOO_FAR, NODE_EV_OFF_PATH, NODE_EV_SOLVE_FAILED,
@@ -105,6 +111,8 @@ BATCH_SYMBOLS = [
     "nmpc_batch_destroy", "nmpc_batch_set_params", "nmpc_batch_get_params", "nmpc_batch_init_iterate",
     "nmpc_batch_solve", "nmpc_batch_solve_iterate", "nmpc_batch_run", "nmpc_batch_run_path", "nmpc_batch_follow_path", "nmpc_batch_node_tick", "nmpc_node_params_default",
     "nmpc_batch_node_tick_queue", "nmpc_path_queue_default", "nmpc_batch_state", "nmpc_batch_warm_state", "nmpc_batch_warm_rule", "nmpc_batch_plan", "nmpc_batch_plan_ex", "nmpc_batch_set_record_layout", "nmpc_batch_forget_warm", "nmpc_batch_set_kernel", "nmpc_batch_set_schedule",
+    "nmpc_batch_set_robot_params", "nmpc_batch_set_robot_limits", "nmpc_batch_robot_params",
+    "nmpc_batch_clear_robot_params",
     "nmpc_fleet_sim_step", "nmpc_fleet_sim_step_renew", "nmpc_fleet_hash",
     "nmpc_last_error", "nmpc_version", "nmpc_path_discretize", "nmpc_path_nearest", "nmpc_codegen_default", "nmpc_capsule_new",
     "nmpc_capsule_delete", "nmpc_capsule_create", "nmpc_capsule_reset", "nmpc_capsule_update_params",
@@ -173,6 +181,10 @@ def lib():
     L.nmpc_batch_plan.argtypes = [vp, ctypes.c_int, c_int_p, c_int_p, c_int_p]
     L.nmpc_batch_plan_ex.argtypes = [vp, i, i, ctypes.POINTER(LaunchPlan)]
     L.nmpc_batch_set_record_layout.argtypes = [vp, i]
+    L.nmpc_batch_set_robot_params.argtypes = [vp, i, ctypes.POINTER(RobotParamsStruct), vp, vp]
+    L.nmpc_batch_set_robot_limits.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]
+    L.nmpc_batch_robot_params.argtypes = [vp, ctypes.POINTER(vp), c_int_p, c_int_p]
+    L.nmpc_batch_clear_robot_params.argtypes = [vp]
     L.nmpc_fleet_sim_step.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     L.nmpc_fleet_sim_step_renew.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(FleetRenew), vp]
     L.nmpc_fleet_hash.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint]

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from ._lib import (KERNELS, MODEL_IDS, PLAN_MODES, REC_LAYOUTS, SCHEDULES, FleetRenew, FleetStats, LaunchPlan,
-                   ModelParams, NodeParamsStruct, check, default_params, lib, model_dims)
+                   ModelParams, NodeParamsStruct, RobotParamsStruct, check, default_params, lib, model_dims)
 
 
 def _ptr(t, dtype=None, shape=None, name="argument"):
@@ -177,13 +177,70 @@ class BatchSolver:
         check(lib().nmpc_batch_forget_warm(self._h, B, _ptr(mask, U8, (B,), "mask"), _stream(stream)),
               "nmpc_batch_forget_warm")
 
+    def set_robot_params(self, lbx=None, ubx=None, lbu=None, ubu=None, W=None, W_e=None, mask=None, stream=None):
+        """Per-robot bounds and weights (nmpc_batch_set_robot_params): each argument a float32 device tensor [n][B]
+        (n = nbx, nbx, nbu, nbu, ny, nx) or None (those rows stay); mask uint8 [B] selects the robots (None: all).
+        One launch on the stream; from then on every launch of this solver takes each robot's values from the table
+        (until clear_robot_params)."""
+        rows = dict(lbx=(lbx, self.nbx), ubx=(ubx, self.nbx), lbu=(lbu, self.nbu), ubu=(ubu, self.nbu),
+                    W=(W, self.ny), W_e=(W_e, self.nx))
+        given = [t for t, _ in rows.values() if t is not None]
+        if not given:
+            raise ValueError("set_robot_params: no field given")
+        B = self._batch_of(given[0])
+        rp = RobotParamsStruct(**{k: _ptr(t, F32, (n, B), k) for k, (t, n) in rows.items()})
+        check(lib().nmpc_batch_set_robot_params(self._h, B, ctypes.byref(rp), _ptr(mask, U8, (B,), "mask"),
+                                                _stream(stream)), "nmpc_batch_set_robot_params")
+
+    def set_robot_limits(self, v_max=None, a_max=None, alpha_min=None, alpha_max=None, dalpha_max=None, mask=None,
+                         stream=None):
+        """The batched nmpc_model_params_set_limits (nmpc_batch_set_robot_limits): float32 device tensors [B], each
+        optional; the steering ones are read for tric only. mask as set_robot_params."""
+        arrs = dict(v_max=v_max, a_max=a_max, alpha_min=alpha_min, alpha_max=alpha_max, dalpha_max=dalpha_max)
+        given = [t for t in arrs.values() if t is not None]
+        if not given:
+            raise ValueError("set_robot_limits: no limit given")
+        B = given[0].shape[0]
+        if not 0 <= B <= self.capacity:
+            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        check(lib().nmpc_batch_set_robot_limits(self._h, B, *[_ptr(t, F32, (B,), k) for k, t in arrs.items()],
+                                                _ptr(mask, U8, (B,), "mask"), _stream(stream)),
+              "nmpc_batch_set_robot_limits")
+
+    def robot_params(self):
+        """View of the per-robot table [rows][cap] (rows lbx ubx lbu ubu W W_e), or None while it is off
+        (nmpc_batch_robot_params)."""
+        tb, rows, stride = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        check(lib().nmpc_batch_robot_params(self._h, ctypes.byref(tb), ctypes.byref(rows), ctypes.byref(stride)),
+              "nmpc_batch_robot_params")
+        return _DeviceView(tb.value, (rows.value, stride.value), self.device) if tb.value else None
+
+    def clear_robot_params(self):
+        """Turn the per-robot table off: launches use the handle's parameters again."""
+        check(lib().nmpc_batch_clear_robot_params(self._h), "nmpc_batch_clear_robot_params")
+
     def save_state(self):
-        """Device copies of everything a solve reads from the handle (iterate, carried refs, warm start)."""
-        return [v.to_tensor() for v in self.state() + self.warm_state()]
+        """Device copies of everything a solve reads from the handle (iterate, carried refs, warm start, and the
+        per-robot table as a sixth entry when it is on)."""
+        saved = [v.to_tensor() for v in self.state() + self.warm_state()]
+        rp = self.robot_params()
+        return saved + [rp.to_tensor()] if rp is not None else saved
 
     def restore_state(self, saved):
         for v, t in zip(self.state() + self.warm_state(), saved):
             v.copy_from(t)
+        if len(saved) > 5:
+            # the table's rows, written through the writer (which allocates and switches the table on)
+            t = saved[5].to(self.device)
+            cuts, off = {}, 0
+            for k, n in (("lbx", self.nbx), ("ubx", self.nbx), ("lbu", self.nbu), ("ubu", self.nbu), ("W", self.ny),
+                         ("W_e", self.nx)):
+                cuts[k] = t[off:off + n].contiguous()
+                off += n
+            self.set_robot_params(**cuts)
+            torch.cuda.synchronize()
+        else:
+            self.clear_robot_params()
 
     def empty(self, *shape, dtype=torch.float32):
         return torch.empty(*shape, dtype=dtype, device=self.device)

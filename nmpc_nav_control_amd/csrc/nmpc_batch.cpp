@@ -59,6 +59,11 @@ struct nmpc_batch {
     unsigned char* node_active = nullptr;
     int* node_n = nullptr;
     int* node_status = nullptr;
+    // per-robot bounds and weights (nmpc_batch_set_robot_params): the table [rp.off[kRpFields]][capacity], allocated
+    // by the first writer; rp_on: launches read it (resident_args)
+    float* rparams = nullptr;
+    RpRows rp{};
+    bool rp_on = false;
 #ifdef NMPC_HYBRID
     // hybrid launch (A/B build only, -DNMPC_HYBRID, NMPC_AMD_HYBRID=H): in a team-kernel launch the robots whose last
     // IPM count was >= H (at most hybrid_cap of them, the hardest first) run the segmented row-parallel kernel (one
@@ -372,7 +377,30 @@ KArgs resident_args(const nmpc_batch* b, int B)
     a.ubar = b->ubar;
     a.carried = b->carried;
     a.scratch = b->scratch;
+    if (b->rp_on) a.rparams = b->rparams;
     return a;
+}
+
+// The per-robot table ready for a writer on stream s: allocated at the first call, and when it was off filled with
+// the handle's own parameters (KParams' fp32 values, so a table nobody wrote to solves what the handle solves)
+int rp_table(nmpc_batch* b, hipStream_t s)
+{
+    if (b->rp_on) return NMPC_OK;
+    const int rows = b->rp.off[kRpFields];
+    if (!b->rparams) {
+        const hipError_t e = hipMalloc(&b->rparams, sizeof(float) * (size_t)rows * (size_t)b->capacity);
+        if (e != hipSuccess) return hip_err(e, "hipMalloc");
+    }
+    RpColumn col;
+    std::memset(&col, 0, sizeof(col));
+    const KParams& k = b->kp;
+    for (int i = 0; i < b->nbx; i++) { col.v[b->rp.off[kRpLbx] + i] = k.lbx[i]; col.v[b->rp.off[kRpUbx] + i] = k.ubx[i]; }
+    for (int i = 0; i < b->nbu; i++) { col.v[b->rp.off[kRpLbu] + i] = k.lbu[i]; col.v[b->rp.off[kRpUbu] + i] = k.ubu[i]; }
+    for (int i = 0; i < b->ny; i++) col.v[b->rp.off[kRpW] + i] = k.W[i];
+    for (int i = 0; i < b->nx; i++) col.v[b->rp.off[kRpWe] + i] = k.We[i];
+    const int rc = hip_err(launch_rp_fill(b->rparams, b->capacity, rows, col, s), "robot_params fill launch");
+    if (rc == NMPC_OK) b->rp_on = true;
+    return rc;
 }
 
 // ... with the inputs and outputs every run-mode launch has; the reference (traj or the path march) is the caller's
@@ -541,6 +569,7 @@ int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** o
     dims_of(prm->model, &b->nx, &b->nu, &b->nbx, &b->nbu, &np);
     b->ny = b->nx + b->nu;
     b->kp = to_kparams(*prm, b->nx, b->nu, b->nbx, b->nbu);
+    b->rp = rp_rows(b->nx, b->nu, b->nbx, b->nbu);
     if (const char* sv = std::getenv("NMPC_AMD_SCHED")) {  // off | auto | sorted | interleaved
         const char* names[5] = {"off", "auto", "sorted", "interleaved", "spread"};
         for (int i = 0; i < 5; i++)
@@ -615,6 +644,7 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->node_active);
     (void)hipFree(b->node_n);
     (void)hipFree(b->node_status);
+    (void)hipFree(b->rparams);
 #ifdef NMPC_HYBRID
     (void)hipFree(b->hyb_n);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
@@ -974,6 +1004,53 @@ int nmpc_batch_forget_warm(nmpc_batch* b, int B, const unsigned char* mask, void
 {
     if (const int rc = check_batch(b, B)) return rc;
     return hip_err(launch_forget_warm(b->warm, mask, B, (hipStream_t)stream), "forget_warm launch");
+}
+
+int nmpc_batch_set_robot_params(nmpc_batch* b, int B, const nmpc_robot_params* rp, const unsigned char* mask,
+                                void* stream)
+{
+    // the checks that need no handle come first
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!rp) return set_err(NMPC_ERR_ARG, "robot params is NULL");
+    if (!rp->lbx && !rp->ubx && !rp->lbu && !rp->ubu && !rp->W && !rp->W_e)
+        return set_err(NMPC_ERR_ARG, "robot params: every field is NULL");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (B == 0) return NMPC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = rp_table(b, s)) return rc;
+    return hip_err(launch_rp_set(b->rparams, b->capacity, B, b->rp, *rp, mask, s), "robot_params launch");
+}
+
+int nmpc_batch_set_robot_limits(nmpc_batch* b, int B, const float* v_max, const float* a_max, const float* alpha_min,
+                                const float* alpha_max, const float* dalpha_max, const unsigned char* mask,
+                                void* stream)
+{
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!v_max && !a_max && !alpha_min && !alpha_max && !dalpha_max)
+        return set_err(NMPC_ERR_ARG, "robot limits: every array is NULL");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (B == 0) return NMPC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = rp_table(b, s)) return rc;
+    return hip_err(launch_rp_limits(b->rparams, b->capacity, B, b->rp, b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0,
+                                    v_max, a_max, alpha_min, alpha_max, dalpha_max, mask, s),
+                   "robot_limits launch");
+}
+
+int nmpc_batch_robot_params(nmpc_batch* b, float** table, int* rows, int* stride)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (table) *table = b->rp_on ? b->rparams : nullptr;
+    if (rows) *rows = b->rp.off[kRpFields];
+    if (stride) *stride = b->capacity;
+    return NMPC_OK;
+}
+
+int nmpc_batch_clear_robot_params(nmpc_batch* b)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    b->rp_on = false;  // (the allocation stays for the next writer, which refills it)
+    return NMPC_OK;
 }
 
 int nmpc_batch_set_record_layout(nmpc_batch* b, int layout)

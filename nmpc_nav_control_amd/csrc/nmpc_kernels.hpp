@@ -97,6 +97,30 @@ struct KArgs {
     float* stage_out_h;
     const float* stage_out_d;
     int stage_out_n;
+    // per-robot bounds and weights (robot_params.hip): the handle's table [rows][sstride], rows as rp_rows() of the
+    // model lays them out; nullptr: the table is off and every robot takes KParams' values. (The row offsets are
+    // compile-time values of the model in the kernels, not launch arguments: the team kernel has no scalar registers
+    // to spare.)
+    const float* rparams;
+};
+
+// Rows of the per-robot table, in this order: lbx[NBX] ubx[NBX] lbu[NBU] ubu[NBU] W[NY] W_e[NX]
+enum RpField { kRpLbx = 0, kRpUbx, kRpLbu, kRpUbu, kRpW, kRpWe, kRpFields };
+struct RpRows {
+    int off[kRpFields + 1];  // first row of each field; off[kRpFields] = rows of the table
+};
+__host__ __device__ constexpr RpRows rp_rows(int nx, int nu, int nbx, int nbu)
+{
+    const int n[kRpFields] = {nbx, nbx, nbu, nbu, nx + nu, nx};
+    RpRows r{};
+    r.off[0] = 0;
+    for (int f = 0; f < kRpFields; f++) r.off[f + 1] = r.off[f] + n[f];
+    return r;
+}
+constexpr int kRpRowsMax = 48;  // omni4: 4 * 4 + 15 + 11 = 42
+// one robot's column of the table (the handle's own parameters: launch_rp_fill's kernel argument)
+struct RpColumn {
+    float v[kRpRowsMax];
 };
 
 template <class M>
@@ -127,6 +151,15 @@ hipError_t launch_hybrid_order(const int* key, int B, int H, int cap, int* order
 hipError_t launch_init_iterate(float* xbar, float* ubar, float* carried, unsigned char* warm, int B, int stride, int N,
                                int nx, int nu, int nbx, int mode, hipStream_t stream);
 hipError_t launch_forget_warm(unsigned char* warm, const unsigned char* mask, int B, hipStream_t stream);
+// the per-robot table's writers (robot_params.hip), each one launch: every robot's column = col (the first `cap`
+// robots); the rows of the non-NULL fields of rp ([n][B] each) for the robots with mask[i] != 0 (nullptr: all); and
+// the batched nmpc_model_params_set_limits (each array [B] or nullptr: those rows stay)
+hipError_t launch_rp_fill(float* table, int cap, int rows, const RpColumn& col, hipStream_t stream);
+hipError_t launch_rp_set(float* table, int cap, int B, const RpRows& rr, const nmpc_robot_params& rp,
+                         const unsigned char* mask, hipStream_t stream);
+hipError_t launch_rp_limits(float* table, int cap, int B, const RpRows& rr, int tric, const float* v_max,
+                            const float* a_max, const float* alpha_min, const float* alpha_max,
+                            const float* dalpha_max, const unsigned char* mask, hipStream_t stream);
 hipError_t launch_path_discretize(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
                                   const double* nearest_u, double period, int num_poses, int holo, float* traj,
                                   double* traj64, hipStream_t stream);

@@ -242,7 +242,7 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     const size_t S = (size_t)a.stride;
     const size_t Bn = (size_t)a.B;
     // this lane's roles, stage weight and box (sqp_steps.hpp)
-    const LaneCtx<M> lc = lane_ctx<M>(P, r);
+    const LaneCtx<M> lc = lane_ctx<M>(P, a, inst, r);
     const bool lv = lc.lv, is_u = lc.is_u, is_x = lc.is_x, has_b = lc.has_b;
     const int xi = lc.xi;
     const float sc = P.dt, w_lane = lc.w_lane, h_stage = lc.h_stage, lo_b = lc.lo_b, hi_b = lc.hi_b;
@@ -551,7 +551,9 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     if (mode == kModeRun && P.terminal_hack)
         we_lane = terminal_weight(lc, we_lane, s_ref[N * 3] == s_ref[(N - 1) * 3] && s_ref[N * 3 + 1] == s_ref[(N - 1) * 3 + 1] &&
                                                    s_ref[N * 3 + 2] == s_ref[(N - 1) * 3 + 2]);
-    const float lam_thr = P.infeas_lam * fmaxf(1.0f, fmaxf(P.wmax, row_max16(is_x ? we_lane : 0.0f)) * 0.1f);
+    // (the robot's own largest stage weight when the per-robot table is on)
+    const float wmax = a.rparams ? row_max16(w_lane) : P.wmax;
+    const float lam_thr = P.infeas_lam * fmaxf(1.0f, fmaxf(wmax, row_max16(is_x ? we_lane : 0.0f)) * 0.1f);
     float sum_c0 = 0.0f;
     for (int j = 0; j < NR; j++) {
         const int kr = j * ROWS + q;

@@ -99,8 +99,10 @@ __device__ __attribute__((aligned(16))) float g_rec_sentinel[8] = {kFar, kFar, 0
 // a.segs set). As runtime arguments their branches inside P0's stage loop (reference unwrap, yref or pose-reference
 // loads, and a pose load from either LDS or global memory, i.e. a flat load) made the compiler's waits drain the
 // whole memory counter, the stage's record stores and the prefetched rows included
+// RP: the launch reads the handle's per-robot table of bounds and weights (KArgs::rparams != nullptr; the launcher
+// picks it from the pointer). Table-off launches run the RP = false instantiations, which do not mention the table
 constexpr int kModeRunPath = 2;
-template <class M, bool MS, bool SD, int MODE, bool SP>
+template <class M, bool MS, bool SD, int MODE, bool SP, bool RP>
 __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 {
     constexpr int mode = MODE == kModeRunPath ? kModeRun : MODE;
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     const size_t Bn = (size_t)a.B;
     const int inst = a.order ? a.order[hoff + team] : team;  // difficulty-ordered placement (schedule.hip)
     // this lane's roles, stage weight and box (sqp_steps.hpp)
-    const LaneCtx<M> lc = lane_ctx<M>(P, r);
+    const LaneCtx<M> lc = lane_ctx<M, RP>(P, a, inst, r);
     const bool lv = lc.lv, is_u = lc.is_u, is_x = lc.is_x, has_b = lc.has_b;
     const int xi = lc.xi, cx = lc.cx;
     const float sc = P.dt, w_lane = lc.w_lane, h_stage = lc.h_stage, lo_b = lc.lo_b, hi_b = lc.hi_b;
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 
     // ---- x0 (every lane keeps the full vector) ----------------------------------------------------------
     float x0[NX];
-    const X0Lane xl = load_x0<M>(P, a, mode, inst, lc, x0);
+    const X0Lane xl = load_x0<M, RP>(P, a, mode, inst, lc, x0);
     const float pose_th = xl.pose_th, x0_lane = xl.x0_lane;
     float we_lane = xl.we_lane;  // (run mode: + the terminal hack, P0's stage N)
 
@@ -525,7 +527,9 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 
     STAMP(1);
     // infeasibility threshold of this robot: qp_infeas_lambda scaled by its largest weight (terminal hack included)
-    const float lam_thr = P.infeas_lam * fmaxf(1.0f, fmaxf(P.wmax, row_max16(is_x ? we_lane : 0.0f)) * 0.1f);
+    // (the robot's own largest stage weight when the per-robot table is on)
+    const float wmax = (RP && a.rparams) ? row_max16(w_lane) : P.wmax;
+    const float lam_thr = P.infeas_lam * fmaxf(1.0f, fmaxf(wmax, row_max16(is_x ? we_lane : 0.0f)) * 0.1f);
     const int m = N * NU + N * M::NBX;
     const float inv_m2 = 0.5f / (float)m;
     sum_c0 = row_sum16(lv ? sum_c0 : 0.0f);
@@ -1106,9 +1110,15 @@ hipError_t launch_sqp_rti_team(const KParams& P, const KArgs& a, int mode, hipSt
     const int km = mode != kModeRun ? kModeSolve : (a.segs ? kModeRunPath : kModeRun);
     auto pick2 = [&](auto msc, auto sdc, auto spc) {
         constexpr bool ms = decltype(msc)::value, sd = decltype(sdc)::value, sp = decltype(spc)::value;
-        if (km == kModeRunPath) go(k_sqp_rti_team<M, ms, sd, kModeRunPath, sp>);
-        else if (km == kModeRun) go(k_sqp_rti_team<M, ms, sd, kModeRun, sp>);
-        else go(k_sqp_rti_team<M, ms, sd, kModeSolve, sp>);
+        auto pick3 = [&](auto rpc) {
+            constexpr bool rp = decltype(rpc)::value;
+            if (km == kModeRunPath) go(k_sqp_rti_team<M, ms, sd, kModeRunPath, sp, rp>);
+            else if (km == kModeRun) go(k_sqp_rti_team<M, ms, sd, kModeRun, sp, rp>);
+            else go(k_sqp_rti_team<M, ms, sd, kModeSolve, sp, rp>);
+        };
+        // the per-robot table: its own instantiations (sqp_steps.hpp lane_ctx)
+        if (a.rparams) pick3(std::true_type{});
+        else pick3(std::false_type{});
     };
     // record layout: tric always split, diff per launch (a.rec_split), omni4 and Mehrotra never
     auto pick = [&](auto msc, auto sdc) {

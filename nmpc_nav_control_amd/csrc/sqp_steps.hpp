@@ -42,8 +42,13 @@ struct LaneCtx {
     float w_lane, h_stage;  // this lane's stage weight, and dt times it
     float lo_b, hi_b;       // this lane's box
 };
-template <class M>
-__device__ __forceinline__ LaneCtx<M> lane_ctx(const KParams& P, int r)
+// a: the launch (its per-robot table, KArgs::rparams), inst: the robot. Table on: this lane's three values from the
+// robot's column, one load each, here in the prologue (idle lanes read rows of slot 0's kind and drop them). A NaN
+// bound makes the lane's weight NaN, so the robot fails alone with status 1, as it does on a NaN input.
+// TBL = false compiles the table out (the team kernel's table-off instantiations: even a branch that is never taken
+// moved its scalar register allocation and cost the metric config 0.9 %, profiles/r07/ab/robot_params.txt)
+template <class M, bool TBL = true>
+__device__ __forceinline__ LaneCtx<M> lane_ctx(const KParams& P, const KArgs& a, int inst, int r)
 {
     constexpr int NX = M::NX, NU = M::NU;
     LaneCtx<M> c;
@@ -53,18 +58,32 @@ __device__ __forceinline__ LaneCtx<M> lane_ctx(const KParams& P, int r)
     c.xi = c.is_x ? r - NU : 0;
     c.cx = c.is_x ? xcomp<M>(c.xi) : -1;
     c.has_b = c.is_u || c.cx >= 0;
-    // this lane's stage weight, read once: indexed by the lane, the W entries are vector loads from the kernel
-    // arguments, and inside P0's loop each one waited on vmcnt(0), i.e. on the previous stage's record stores
-    c.w_lane = c.is_u ? P.W[NX + r] : (c.is_x ? P.W[c.xi] : 0.0f);
+    if (TBL && a.rparams) {
+        constexpr RpRows RR = rp_rows(NX, NU, M::NBX, M::NBU);
+        const float* const t = a.rparams + inst;
+        const size_t C = (size_t)a.sstride;
+        const int bj = c.is_u ? r : (c.cx >= 0 ? c.cx : 0);
+        const float w = t[(size_t)(RR.off[kRpW] + (c.is_u ? NX + r : c.xi)) * C];
+        const float lo = t[(size_t)((c.is_u ? RR.off[kRpLbu] : RR.off[kRpLbx]) + bj) * C];
+        const float hi = t[(size_t)((c.is_u ? RR.off[kRpUbu] : RR.off[kRpUbx]) + bj) * C];
+        const bool nan_b = c.has_b && (lo != lo || hi != hi);
+        c.w_lane = c.lv ? (nan_b ? __builtin_nanf("") : w) : 0.0f;
+        c.lo_b = c.has_b ? lo : 0.0f;
+        c.hi_b = c.has_b ? hi : 0.0f;
+    } else {
+        // this lane's stage weight, read once: indexed by the lane, the W entries are vector loads from the kernel
+        // arguments, and inside P0's loop each one waited on vmcnt(0), i.e. on the previous stage's record stores
+        c.w_lane = c.is_u ? P.W[NX + r] : (c.is_x ? P.W[c.xi] : 0.0f);
+        c.lo_b = 0.0f;
+        c.hi_b = 0.0f;
+#pragma unroll
+        for (int q = 0; q < NU; q++)
+            if (r == q) { c.lo_b = P.lbu[q]; c.hi_b = P.ubu[q]; }
+#pragma unroll
+        for (int b = 0; b < M::NBX; b++)
+            if (c.cx == b) { c.lo_b = P.lbx[b]; c.hi_b = P.ubx[b]; }
+    }
     c.h_stage = P.dt * c.w_lane;
-    c.lo_b = 0.0f;
-    c.hi_b = 0.0f;
-#pragma unroll
-    for (int q = 0; q < NU; q++)
-        if (r == q) { c.lo_b = P.lbu[q]; c.hi_b = P.ubu[q]; }
-#pragma unroll
-    for (int b = 0; b < M::NBX; b++)
-        if (c.cx == b) { c.lo_b = P.lbx[b]; c.hi_b = P.ubx[b]; }
     return c;
 }
 
@@ -72,11 +91,12 @@ __device__ __forceinline__ LaneCtx<M> lane_ctx(const KParams& P, int r)
 struct X0Lane {
     float pose_th;  // run mode: the pose's heading, where the reference unwrap starts
     float x0_lane;  // this lane's entry of x0 (state lanes)
-    float we_lane;  // terminal weight of this lane's state (solve mode: caller's W_e; run mode: constructor W_e)
+    float we_lane;  // terminal weight of this lane's state: the caller's W_e (solve mode), else the robot's table row,
+                    // else the constructor W_e
 };
 // run mode: pose, direct kinematics of the measured velocity, and the carried refs on the bounded states
 // (NMPCNavControlDiff.cpp:88-101); solve mode: the caller's x0
-template <class M>
+template <class M, bool TBL = true>
 __device__ __forceinline__ X0Lane load_x0(const KParams& P, const KArgs& a, int mode, int inst, const LaneCtx<M>& c,
                                           float (&x0)[M::NX])
 {
@@ -104,7 +124,12 @@ __device__ __forceinline__ X0Lane load_x0(const KParams& P, const KArgs& a, int 
     for (int j = 0; j < NX; j++)
         if (c.xi == j) o.x0_lane = x0[j];
     o.we_lane = 0.0f;
-    if (c.is_x) o.we_lane = (mode != kModeRun && a.We) ? a.We[(size_t)c.xi * Bn + inst] : P.We[c.xi];
+    if (c.is_x) {
+        if (mode != kModeRun && a.We) o.we_lane = a.We[(size_t)c.xi * Bn + inst];
+        else if (TBL && a.rparams)
+            o.we_lane = a.rparams[(size_t)(rp_rows(NX, M::NU, M::NBX, M::NBU).off[kRpWe] + c.xi) * (size_t)a.sstride + inst];
+        else o.we_lane = P.We[c.xi];
+    }
     return o;
 }
 
