@@ -96,7 +96,8 @@ int nmpc_model_params_set_limits(nmpc_model_params* prm, double v_max, double a_
 int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** out);
 int nmpc_batch_destroy(nmpc_batch* b);
 /* Replace weights / bounds / parameters / QP options (model and N must not change). While the per-robot table is
- * on (nmpc_batch_set_robot_params below), lbx, ubx, lbu, ubu, W and W_e do not reach a launch. */
+ * on (nmpc_batch_set_robot_params below), lbx, ubx, lbu, ubu, W and W_e do not reach a launch; while the stage table
+ * is on (nmpc_batch_set_stage_bounds below), the four bound fields do not. */
 int nmpc_batch_set_params(nmpc_batch* b, const nmpc_model_params* prm);
 int nmpc_batch_get_params(const nmpc_batch* b, nmpc_model_params* prm);
 /* Re-initialise instances [0, B): mode 0 = create semantics (x = [0,0,pi,0,...], u = 0, carried ref states 0);
@@ -394,8 +395,9 @@ int nmpc_batch_warm_state(nmpc_batch* b, unsigned char** warm, float** scratch, 
  *     robot is affected, and the robot keeps its iterate and carried refs and gets a stop command, as after any
  *     failed solve. The input weights R must stay > 0, as nmpc_batch_create requires of the handle's.
  *   - Two scopes stay with the handle: the model parameters p (b, tau_v, ...), which the kernels take as uniform
- *     operands (the constant rows of the stage Jacobian are shared by the robots of a wave), and anything that
- *     varies along the horizon (one W and one box per robot, for every stage).
+ *     operands (the constant rows of the stage Jacobian are shared by the robots of a wave), and weights that vary
+ *     along the horizon (one W per robot, for every stage). Bounds that vary along the horizon have a table of their
+ *     own (nmpc_batch_set_stage_bounds below), which then replaces this table's four bound rows.
  * Argument errors (NMPC_ERR_ARG): B out of range, rp NULL, every field NULL (nmpc_batch_set_robot_limits: every
  * array NULL), a NULL handle. */
 typedef struct nmpc_robot_params {
@@ -423,6 +425,65 @@ int nmpc_batch_robot_params(nmpc_batch* b, float** table, int* rows, int* stride
 /* Turn the table off: launches use the handle's parameters again. The next writer call starts a fresh table from the
  * handle's parameters. (Host-side switch: it applies to the launches enqueued after it.) */
 int nmpc_batch_clear_robot_params(nmpc_batch* b);
+
+/* Stage-varying bounds. One box per robot holds at every stage of the horizon, so a speed limit that drops when a
+ * robot enters a zone can only be applied at once, and a robot that is faster than the new limit gets an infeasible
+ * QP (status 4, stop command). With a box per stage the limit can come down along the horizon and the solve brakes
+ * into it. The handle therefore owns a second device table, the stage table: for every robot and every stage
+ * k = 0..N the rows
+ *     lbx[NBX] ubx[NBX] lbu[NBU] ubu[NBU]
+ * in fp32. It is allocated by the first writer call below. Its size is (N+1) * (2 NBX + 2 NBU) * capacity * 4 bytes:
+ * 5.4 MB for diff at N = 40 and 4096 robots, 86 MB at 65536. The bounded-state rows of stages 1..N and the input rows
+ * of stages 0..N-1 reach a launch; the state rows of stage 0 and the input rows of stage N are allocated and never
+ * interpreted (a NaN there is harmless). The device layout is the library's business ([stage][robot][row] today: one
+ * robot's rows of a stage share a cache line); the checkpoint view is opaque bytes.
+ * Rules:
+ *   - While the stage table is on, every launch of the handle -- nmpc_batch_solve, _solve_iterate, _run, _run_path,
+ *     _follow_path and both node ticks -- takes each robot's box at stage k from it. W and W_e still come from the
+ *     per-robot table if that is on, else from the handle (a caller's We still wins in solve mode). The four bound
+ *     rows of the per-robot table, and the handle's, then do not reach a launch: they are what a stage table
+ *     allocated or cleared later starts from (the robot's column if the per-robot table is on at that moment, else
+ *     the handle's values, at every stage).
+ *   - While it is off (never written, or after nmpc_batch_clear_stage_bounds) every launch computes exactly what it
+ *     computed without this interface.
+ *   - Each writer is one small launch on `stream`, with no host synchronisation and no host-side validation.
+ *   - A NaN in a bound the QP uses fails that robot alone with status 1; lb > ub at a stage gives that robot a
+ *     nonzero status through the solver's existing exits. The robot keeps its iterate and carried refs and gets a
+ *     stop command, as after any failed solve; no other robot is affected. Warm flags are left alone.
+ *   - nmpc_batch_shift_stage_bounds moves a profile one tick down the horizon. A shift by one stage per tick matches
+ *     the plant only when dt_ctrl == dt, which holds for the defaults (both 1/40); otherwise upload the profile
+ *     again, sampled at the solver's stage times.
+ *   - Still with the handle: stage-varying weights (the stage weight is read inside every IPM iteration, so a weight
+ *     per stage would cost the hot loop), the model parameters p, and the capsule ABI, which keeps rejecting
+ *     stage-varying data.
+ * Argument errors (NMPC_ERR_ARG): B out of range, sb NULL, every field NULL (nmpc_batch_set_stage_limits: every array
+ * NULL), n < 0, a NULL handle. */
+typedef struct nmpc_stage_bounds {
+    const float* lbx; /* [N+1][NBX][B] device, or NULL: those rows stay as they are */
+    const float* ubx; /* [N+1][NBX][B] */
+    const float* lbu; /* [N][NBU][B] */
+    const float* ubu; /* [N][NBU][B] */
+} nmpc_stage_bounds;
+/* Write the rows of the non-NULL fields at every stage for robots [0, B) where mask[i] != 0 (mask [B] device, NULL:
+ * all). */
+int nmpc_batch_set_stage_bounds(nmpc_batch* b, int B, const nmpc_stage_bounds* sb, const unsigned char* mask,
+                                void* stream);
+/* The batched, per-stage nmpc_model_params_set_limits, with the mapping of nmpc_batch_set_robot_limits: v_max,
+ * alpha_min, alpha_max are device arrays [N+1][B], a_max and dalpha_max [N][B]; each may be NULL (those rows stay).
+ * The three steering arrays are read for tric only. mask as above. */
+int nmpc_batch_set_stage_limits(nmpc_batch* b, int B, const float* v_max, const float* a_max, const float* alpha_min,
+                                const float* alpha_max, const float* dalpha_max, const unsigned char* mask,
+                                void* stream);
+/* Receding horizon: stage k takes stage min(k + n, last) of the same row (last = N for state rows, N-1 for input
+ * rows), n >= 0, for the robots with mask[i] != 0; the last stage is repeated. One thread per (row, robot) walks k
+ * upwards, so the shift is in place. */
+int nmpc_batch_shift_stage_bounds(nmpc_batch* b, int B, int n, const unsigned char* mask, void* stream);
+/* The table's device view for checkpoints: *table and *bytes (opaque: copy it whole, into a handle of the same model,
+ * N and capacity), or NULL / 0 while the table is off. Each output may be NULL. */
+int nmpc_batch_stage_bounds(nmpc_batch* b, void** table, size_t* bytes);
+/* Turn the stage table off: launches use the per-robot table's or the handle's one box again. The next writer call
+ * starts a fresh table. (Host-side switch: it applies to the launches enqueued after it.) */
+int nmpc_batch_clear_stage_bounds(nmpc_batch* b);
 
 /* Record layout of the team kernel's single-direction scratch records, a per-handle choice fixed at create time
  * and changed only by this call (never by other handles):

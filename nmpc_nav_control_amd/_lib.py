@@ -77,6 +77,12 @@ class RobotParamsStruct(ctypes.Structure):
                 ("W_e", c_void_p)]
 
 
+class StageBoundsStruct(ctypes.Structure):
+    """Mirror of nmpc_stage_bounds (include/nmpc_amd/nmpc_batch.h): device pointers [N+1 or N][n][B], None = rows
+    untouched."""
+    _fields_ = [("lbx", c_void_p), ("ubx", c_void_p), ("lbu", c_void_p), ("ubu", c_void_p)]
+
+
 # NMPC_NODE_* (a robot's state in the node's state machine) and NMPC_NODE_EV_* (what the tick did for it)
 NODE_IDLE, NODE_GOTO_POSE, NODE_FOLLOW_PATH, NODE_BREAK, NODE_ERROR = 0, 1, 2, 3, 4
 (NODE_EV_NONE, NODE_EV_SOLVED, NODE_EV_ARRIVED, NODE_EV_GOAL_TOO_FAR, NODE_EV_OFF_PATH, NODE_EV_SOLVE_FAILED,
@@ -113,6 +119,8 @@ BATCH_SYMBOLS = [
     "nmpc_batch_node_tick_queue", "nmpc_path_queue_default", "nmpc_batch_state", "nmpc_batch_warm_state", "nmpc_batch_warm_rule", "nmpc_batch_plan", "nmpc_batch_plan_ex", "nmpc_batch_set_record_layout", "nmpc_batch_forget_warm", "nmpc_batch_set_kernel", "nmpc_batch_set_schedule",
     "nmpc_batch_set_robot_params", "nmpc_batch_set_robot_limits", "nmpc_batch_robot_params",
     "nmpc_batch_clear_robot_params",
+    "nmpc_batch_set_stage_bounds", "nmpc_batch_set_stage_limits", "nmpc_batch_shift_stage_bounds",
+    "nmpc_batch_stage_bounds", "nmpc_batch_clear_stage_bounds",
     "nmpc_fleet_sim_step", "nmpc_fleet_sim_step_renew", "nmpc_fleet_hash",
     "nmpc_last_error", "nmpc_version", "nmpc_path_discretize", "nmpc_path_nearest", "nmpc_codegen_default", "nmpc_capsule_new",
     "nmpc_capsule_delete", "nmpc_capsule_create", "nmpc_capsule_reset", "nmpc_capsule_update_params",
@@ -185,6 +193,11 @@ def lib():
     L.nmpc_batch_set_robot_limits.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]
     L.nmpc_batch_robot_params.argtypes = [vp, ctypes.POINTER(vp), c_int_p, c_int_p]
     L.nmpc_batch_clear_robot_params.argtypes = [vp]
+    L.nmpc_batch_set_stage_bounds.argtypes = [vp, i, ctypes.POINTER(StageBoundsStruct), vp, vp]
+    L.nmpc_batch_set_stage_limits.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]
+    L.nmpc_batch_shift_stage_bounds.argtypes = [vp, i, i, vp, vp]
+    L.nmpc_batch_stage_bounds.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+    L.nmpc_batch_clear_stage_bounds.argtypes = [vp]
     L.nmpc_fleet_sim_step.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     L.nmpc_fleet_sim_step_renew.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(FleetRenew), vp]
     L.nmpc_fleet_hash.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint]

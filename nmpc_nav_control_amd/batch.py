@@ -9,7 +9,8 @@ import ctypes
 import torch
 
 from ._lib import (KERNELS, MODEL_IDS, PLAN_MODES, REC_LAYOUTS, SCHEDULES, FleetRenew, FleetStats, LaunchPlan,
-                   ModelParams, NodeParamsStruct, RobotParamsStruct, check, default_params, lib, model_dims)
+                   ModelParams, NodeParamsStruct, RobotParamsStruct, StageBoundsStruct, check, default_params, lib,
+                   model_dims)
 
 
 def _ptr(t, dtype=None, shape=None, name="argument"):
@@ -219,16 +220,82 @@ class BatchSolver:
         """Turn the per-robot table off: launches use the handle's parameters again."""
         check(lib().nmpc_batch_clear_robot_params(self._h), "nmpc_batch_clear_robot_params")
 
+    def set_stage_bounds(self, lbx=None, ubx=None, lbu=None, ubu=None, mask=None, stream=None):
+        """Stage-varying bounds (nmpc_batch_set_stage_bounds): lbx / ubx float32 device tensors [N+1][nbx][B], lbu /
+        ubu [N][nbu][B], each optional (those rows stay); mask uint8 [B] selects the robots (None: all). One launch on
+        the stream; from then on every launch of this solver takes each robot's box at stage k from the stage table
+        (until clear_stage_bounds)."""
+        N = self.N
+        rows = dict(lbx=(lbx, N + 1, self.nbx), ubx=(ubx, N + 1, self.nbx), lbu=(lbu, N, self.nbu),
+                    ubu=(ubu, N, self.nbu))
+        given = [t for t, _, _ in rows.values() if t is not None]
+        if not given:
+            raise ValueError("set_stage_bounds: no field given")
+        B = self._batch_last(given[0])
+        sb = StageBoundsStruct(**{k: _ptr(t, F32, (ns, n, B), k) for k, (t, ns, n) in rows.items()})
+        check(lib().nmpc_batch_set_stage_bounds(self._h, B, ctypes.byref(sb), _ptr(mask, U8, (B,), "mask"),
+                                                _stream(stream)), "nmpc_batch_set_stage_bounds")
+
+    def set_stage_limits(self, v_max=None, a_max=None, alpha_min=None, alpha_max=None, dalpha_max=None, mask=None,
+                         stream=None):
+        """The batched, per-stage nmpc_model_params_set_limits (nmpc_batch_set_stage_limits): v_max, alpha_min,
+        alpha_max float32 device tensors [N+1][B], a_max and dalpha_max [N][B], each optional; the steering ones are
+        read for tric only. mask as set_stage_bounds."""
+        N = self.N
+        arrs = dict(v_max=(v_max, N + 1), a_max=(a_max, N), alpha_min=(alpha_min, N + 1), alpha_max=(alpha_max, N + 1),
+                    dalpha_max=(dalpha_max, N))
+        given = [t for t, _ in arrs.values() if t is not None]
+        if not given:
+            raise ValueError("set_stage_limits: no limit given")
+        B = self._batch_last(given[0])
+        check(lib().nmpc_batch_set_stage_limits(self._h, B, *[_ptr(t, F32, (ns, B), k) for k, (t, ns) in arrs.items()],
+                                                _ptr(mask, U8, (B,), "mask"), _stream(stream)),
+              "nmpc_batch_set_stage_limits")
+
+    def shift_stage_bounds(self, n=1, mask=None, B=None, stream=None):
+        """Receding horizon (nmpc_batch_shift_stage_bounds): stage k of every row takes stage min(k + n, last), for the
+        robots where mask != 0 (None: all of the first B, default the capacity)."""
+        if int(n) < 0:
+            raise ValueError("shift_stage_bounds: n must be >= 0")
+        B = self.capacity if B is None else int(B)
+        check(lib().nmpc_batch_shift_stage_bounds(self._h, B, int(n), _ptr(mask, U8, (B,), "mask"), _stream(stream)),
+              "nmpc_batch_shift_stage_bounds")
+
+    def stage_bounds(self):
+        """View of the stage table as opaque bytes [1][bytes] (uint8), or None while it is off
+        (nmpc_batch_stage_bounds)."""
+        tb, nb = ctypes.c_void_p(), ctypes.c_size_t()
+        check(lib().nmpc_batch_stage_bounds(self._h, ctypes.byref(tb), ctypes.byref(nb)), "nmpc_batch_stage_bounds")
+        return _DeviceView(tb.value, (1, nb.value), self.device, torch.uint8) if tb.value else None
+
+    def clear_stage_bounds(self):
+        """Turn the stage table off: launches use one box per robot again."""
+        check(lib().nmpc_batch_clear_stage_bounds(self._h), "nmpc_batch_clear_stage_bounds")
+
     def save_state(self):
-        """Device copies of everything a solve reads from the handle (iterate, carried refs, warm start, and the
-        per-robot table as a sixth entry when it is on)."""
+        """Device copies of everything a solve reads from the handle: iterate, carried refs, warm start (five
+        tensors), then the per-robot table as a tensor when it is on, then the stage table as
+        {"stage_bounds": bytes} when it is on."""
         saved = [v.to_tensor() for v in self.state() + self.warm_state()]
         rp = self.robot_params()
-        return saved + [rp.to_tensor()] if rp is not None else saved
+        if rp is not None:
+            saved.append(rp.to_tensor())
+        sb = self.stage_bounds()
+        if sb is not None:
+            saved.append({"stage_bounds": sb.to_tensor()})
+        return saved
 
     def restore_state(self, saved):
         for v, t in zip(self.state() + self.warm_state(), saved):
             v.copy_from(t)
+        stage = [e["stage_bounds"] for e in saved[5:] if isinstance(e, dict)]
+        saved = [e for e in saved if not isinstance(e, dict)]
+        if stage:
+            # (a shift by no stage allocates the table and switches it on; the bytes then replace its first fill)
+            self.shift_stage_bounds(0)
+            self.stage_bounds().copy_from(stage[0])
+        else:
+            self.clear_stage_bounds()
         if len(saved) > 5:
             # the table's rows, written through the writer (which allocates and switches the table on)
             t = saved[5].to(self.device)
@@ -248,6 +315,13 @@ class BatchSolver:
     def _batch_of(self, t):
         """B of a call, from its first [field][B] input."""
         B = t.shape[1]
+        if not 0 <= B <= self.capacity:
+            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        return B
+
+    def _batch_last(self, t):
+        """B of a stage-table call, from the last dimension of its first input."""
+        B = t.shape[-1]
         if not 0 <= B <= self.capacity:
             raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
         return B

@@ -64,6 +64,10 @@ struct nmpc_batch {
     float* rparams = nullptr;
     RpRows rp{};
     bool rp_on = false;
+    // stage-varying bounds (nmpc_batch_set_stage_bounds): the stage table, (N + 1) * sb_rows * capacity floats (sb_at,
+    // nmpc_kernels.hpp), allocated by the first writer; sb_on: launches read it (resident_args)
+    float* sbounds = nullptr;
+    bool sb_on = false;
 #ifdef NMPC_HYBRID
     // hybrid launch (A/B build only, -DNMPC_HYBRID, NMPC_AMD_HYBRID=H): in a team-kernel launch the robots whose last
     // IPM count was >= H (at most hybrid_cap of them, the hardest first) run the segmented row-parallel kernel (one
@@ -378,6 +382,7 @@ KArgs resident_args(const nmpc_batch* b, int B)
     a.carried = b->carried;
     a.scratch = b->scratch;
     if (b->rp_on) a.rparams = b->rparams;
+    if (b->sb_on) a.sbounds = b->sbounds;
     return a;
 }
 
@@ -400,6 +405,39 @@ int rp_table(nmpc_batch* b, hipStream_t s)
     for (int i = 0; i < b->nx; i++) col.v[b->rp.off[kRpWe] + i] = k.We[i];
     const int rc = hip_err(launch_rp_fill(b->rparams, b->capacity, rows, col, s), "robot_params fill launch");
     if (rc == NMPC_OK) b->rp_on = true;
+    return rc;
+}
+
+SbDims sb_dims(const nmpc_batch* b) { return SbDims{b->prm.N, b->capacity, b->nbx, b->nbu}; }
+size_t sb_bytes(const nmpc_batch* b)
+{
+    return sizeof(float) * (size_t)(b->prm.N + 1) * (size_t)sb_rows(b->nbx, b->nbu) * (size_t)b->capacity;
+}
+
+// The stage table ready for a writer on stream s: allocated at the first call, and when it was off filled at every
+// stage with the box the launches used until now (the robot's column of the per-robot table if that is on, else the
+// handle's fp32 values)
+int sb_table(nmpc_batch* b, hipStream_t s)
+{
+    if (b->sb_on) return NMPC_OK;
+    if (!b->sbounds) {
+        const hipError_t e = hipMalloc(&b->sbounds, sb_bytes(b));
+        if (e != hipSuccess) return hip_err(e, "hipMalloc");
+    }
+    RpColumn col;
+    std::memset(&col, 0, sizeof(col));
+    const KParams& k = b->kp;
+    for (int i = 0; i < b->nbx; i++) {
+        col.v[sb_off(kSbLbx, b->nbx, b->nbu) + i] = k.lbx[i];
+        col.v[sb_off(kSbUbx, b->nbx, b->nbu) + i] = k.ubx[i];
+    }
+    for (int i = 0; i < b->nbu; i++) {
+        col.v[sb_off(kSbLbu, b->nbx, b->nbu) + i] = k.lbu[i];
+        col.v[sb_off(kSbUbu, b->nbx, b->nbu) + i] = k.ubu[i];
+    }
+    const int rc = hip_err(launch_sb_fill(b->sbounds, sb_dims(b), col, b->rp_on ? b->rparams : nullptr, b->rp, s),
+                           "stage_bounds fill launch");
+    if (rc == NMPC_OK) b->sb_on = true;
     return rc;
 }
 
@@ -645,6 +683,7 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->node_n);
     (void)hipFree(b->node_status);
     (void)hipFree(b->rparams);
+    (void)hipFree(b->sbounds);
 #ifdef NMPC_HYBRID
     (void)hipFree(b->hyb_n);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
@@ -1050,6 +1089,63 @@ int nmpc_batch_clear_robot_params(nmpc_batch* b)
 {
     if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
     b->rp_on = false;  // (the allocation stays for the next writer, which refills it)
+    return NMPC_OK;
+}
+
+int nmpc_batch_set_stage_bounds(nmpc_batch* b, int B, const nmpc_stage_bounds* sb, const unsigned char* mask,
+                                void* stream)
+{
+    // the checks that need no handle come first
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!sb) return set_err(NMPC_ERR_ARG, "stage bounds is NULL");
+    if (!sb->lbx && !sb->ubx && !sb->lbu && !sb->ubu)
+        return set_err(NMPC_ERR_ARG, "stage bounds: every field is NULL");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (B == 0) return NMPC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = sb_table(b, s)) return rc;
+    return hip_err(launch_sb_set(b->sbounds, sb_dims(b), B, *sb, mask, s), "stage_bounds launch");
+}
+
+int nmpc_batch_set_stage_limits(nmpc_batch* b, int B, const float* v_max, const float* a_max, const float* alpha_min,
+                                const float* alpha_max, const float* dalpha_max, const unsigned char* mask,
+                                void* stream)
+{
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!v_max && !a_max && !alpha_min && !alpha_max && !dalpha_max)
+        return set_err(NMPC_ERR_ARG, "stage limits: every array is NULL");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (B == 0) return NMPC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = sb_table(b, s)) return rc;
+    return hip_err(launch_sb_limits(b->sbounds, sb_dims(b), B, b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0, v_max,
+                                    a_max, alpha_min, alpha_max, dalpha_max, mask, s),
+                   "stage_limits launch");
+}
+
+int nmpc_batch_shift_stage_bounds(nmpc_batch* b, int B, int n, const unsigned char* mask, void* stream)
+{
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (n < 0) return set_err(NMPC_ERR_ARG, "stage shift: n must be >= 0");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (B == 0) return NMPC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = sb_table(b, s)) return rc;
+    return hip_err(launch_sb_shift(b->sbounds, sb_dims(b), B, n, mask, s), "stage_shift launch");
+}
+
+int nmpc_batch_stage_bounds(nmpc_batch* b, void** table, size_t* bytes)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (table) *table = b->sb_on ? b->sbounds : nullptr;
+    if (bytes) *bytes = b->sb_on ? sb_bytes(b) : 0;
+    return NMPC_OK;
+}
+
+int nmpc_batch_clear_stage_bounds(nmpc_batch* b)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    b->sb_on = false;  // (the allocation stays for the next writer, which refills it)
     return NMPC_OK;
 }
 

@@ -102,6 +102,10 @@ struct KArgs {
     // compile-time values of the model in the kernels, not launch arguments: the team kernel has no scalar registers
     // to spare.)
     const float* rparams;
+    // stage-varying bounds (stage_bounds.hip): the handle's stage table, every robot's box at every stage of the
+    // horizon (sb_at below); nullptr: the table is off and a robot's box is the same at every stage (rparams, else
+    // KParams). While it is on, the bound rows of rparams and of KParams reach no launch
+    const float* sbounds;
 };
 
 // Rows of the per-robot table, in this order: lbx[NBX] ubx[NBX] lbu[NBU] ubu[NBU] W[NY] W_e[NX]
@@ -122,6 +126,27 @@ constexpr int kRpRowsMax = 48;  // omni4: 4 * 4 + 15 + 11 = 42
 struct RpColumn {
     float v[kRpRowsMax];
 };
+
+// The stage table: per stage and robot the rows lbx[NBX] ubx[NBX] lbu[NBU] ubu[NBU], (N + 1) stages, `cap` robots.
+// Laid out [stage][robot][row]: one robot's rows of a stage are one cache line (diff, tric 32 B, omni4 64 B), and the
+// lanes of a DPP row read consecutive floats. (-DNMPC_SB_ROW_MAJOR, A/B only: [stage][row][robot], the per-robot
+// table's orientation; profiles/r07/ab/stage_bounds.txt)
+enum SbField { kSbLbx = 0, kSbUbx, kSbLbu, kSbUbu, kSbFields };
+__host__ __device__ constexpr int sb_rows(int nbx, int nbu) { return 2 * nbx + 2 * nbu; }
+__host__ __device__ constexpr int sb_off(int field, int nbx, int nbu)
+{
+    return field == kSbLbx ? 0 : field == kSbUbx ? nbx : field == kSbLbu ? 2 * nbx : 2 * nbx + nbu;
+}
+// float index of robot i's row `row` at stage k, and the distance from one stage to the next
+__host__ __device__ inline size_t sb_at(int k, int row, int i, int cap, int rows)
+{
+#ifdef NMPC_SB_ROW_MAJOR
+    return ((size_t)k * rows + row) * (size_t)cap + i;
+#else
+    return ((size_t)k * cap + i) * (size_t)rows + row;
+#endif
+}
+__host__ __device__ inline size_t sb_stage_stride(int cap, int rows) { return (size_t)cap * rows; }
 
 template <class M>
 size_t team_scratch_floats(int N, int stride);
@@ -160,6 +185,21 @@ hipError_t launch_rp_set(float* table, int cap, int B, const RpRows& rr, const n
 hipError_t launch_rp_limits(float* table, int cap, int B, const RpRows& rr, int tric, const float* v_max,
                             const float* a_max, const float* alpha_min, const float* alpha_max,
                             const float* dalpha_max, const unsigned char* mask, hipStream_t stream);
+// the stage table's writers (stage_bounds.hip), each one launch. sb: the table, N + 1 stages of `cap` robots.
+// fill: every stage of every robot = the robot's column of the per-robot table rp (rows rr, stride cap) when rp is
+// not nullptr, else col's first sb_rows values (lbx ubx lbu ubu of the handle). set: the non-NULL fields of s for the
+// robots with mask[i] != 0. limits: the per-stage nmpc_model_params_set_limits. shift: stage k = stage min(k + n, last)
+struct SbDims {
+    int N, cap, nbx, nbu;
+};
+hipError_t launch_sb_fill(float* sb, const SbDims& d, const RpColumn& col, const float* rp, const RpRows& rr,
+                          hipStream_t stream);
+hipError_t launch_sb_set(float* sb, const SbDims& d, int B, const nmpc_stage_bounds& s, const unsigned char* mask,
+                         hipStream_t stream);
+hipError_t launch_sb_limits(float* sb, const SbDims& d, int B, int tric, const float* v_max, const float* a_max,
+                            const float* alpha_min, const float* alpha_max, const float* dalpha_max,
+                            const unsigned char* mask, hipStream_t stream);
+hipError_t launch_sb_shift(float* sb, const SbDims& d, int B, int n, const unsigned char* mask, hipStream_t stream);
 hipError_t launch_path_discretize(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
                                   const double* nearest_u, double period, int num_poses, int holo, float* traj,
                                   double* traj64, hipStream_t stream);

@@ -555,6 +555,10 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     const float wmax = a.rparams ? row_max16(w_lane) : P.wmax;
     const float lam_thr = P.infeas_lam * fmaxf(1.0f, fmaxf(wmax, row_max16(is_x ? we_lane : 0.0f)) * 0.1f);
     float sum_c0 = 0.0f;
+    // the stage table (a runtime branch on the pointer, uniform over the launch): each row loads its stage's pair
+    const bool sb_on = a.sbounds != nullptr;
+    StageBox sbx{};
+    if (sb_on) sbx = stage_box_ctx<M>(a, inst, lc, r);
     for (int j = 0; j < NR; j++) {
         const int kr = j * ROWS + q;
         const bool kv = kr <= N;
@@ -570,9 +574,14 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
         const bool valid = vu || vx;
         const float w = vx ? ((k == N) ? we_lane : sc * w_lane) : sc * w_lane;
         rec[R::GR] = valid ? w * (zbar - yr) : 0.0f;
+        float2 box = make_float2(lo_b, hi_b);
+        if (sb_on) {
+            box = stage_box(sbx, k, N);
+            rec[R::GR] = stage_box_poison(rec[R::GR], box, valid && has_b);
+        }
         const float z = vx ? dxk : 0.0f;
         rec[R::Z] = z;
-        const BoundStart b = bound_start(P, zbar, z, lo_b, hi_b, warm, make_float2(st[SL::LL], st[SL::LU]), valid && has_b);
+        const BoundStart b = bound_start(P, zbar, z, box.x, box.y, warm, make_float2(st[SL::LL], st[SL::LU]), valid && has_b);
         rec[R::LB] = b.lb;
         rec[R::UB] = b.ub;
         rec[R::TL] = b.tl;

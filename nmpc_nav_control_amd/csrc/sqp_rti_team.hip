@@ -99,8 +99,9 @@ __device__ __attribute__((aligned(16))) float g_rec_sentinel[8] = {kFar, kFar, 0
 // a.segs set). As runtime arguments their branches inside P0's stage loop (reference unwrap, yref or pose-reference
 // loads, and a pose load from either LDS or global memory, i.e. a flat load) made the compiler's waits drain the
 // whole memory counter, the stage's record stores and the prefetched rows included
-// RP: the launch reads the handle's per-robot table of bounds and weights (KArgs::rparams != nullptr; the launcher
-// picks it from the pointer). Table-off launches run the RP = false instantiations, which do not mention the table
+// RP: the launch reads the handle's per-robot table of bounds and weights or its stage table (KArgs::rparams or
+// KArgs::sbounds != nullptr; the launcher picks it from the pointers). P0 then loads each lane's box per stage
+// (stage_box). Launches with both tables off run the RP = false instantiations, which mention neither table
 constexpr int kModeRunPath = 2;
 template <class M, bool MS, bool SD, int MODE, bool SP, bool RP>
 __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
@@ -134,6 +135,9 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     const bool lv = lc.lv, is_u = lc.is_u, is_x = lc.is_x, has_b = lc.has_b;
     const int xi = lc.xi, cx = lc.cx;
     const float sc = P.dt, w_lane = lc.w_lane, h_stage = lc.h_stage, lo_b = lc.lo_b, hi_b = lc.hi_b;
+    // RP: where P0 loads this lane's box of a stage from (the stage table, else the per-robot table's one box)
+    StageBox sbx{};
+    if constexpr (RP) sbx = stage_box_ctx<M>(a, inst, lc, r);
     // this lane's record of stage k: tbase + k * KS
     // idle slots (r >= NV) alias slot 0's record: their (unpredicated) loads then read valid data and touch no
     // extra cache lines; they never store
@@ -316,8 +320,9 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     // multipliers, the stage record, and the dynamics-feasible initial state of the next stage. Inputs: this
     // lane's iterate entry zbar, its yref entry (solve mode) or the stage's pose ref (run mode), its warm
     // multipliers, the NGV varying Jacobian rows of its column and its defect b_k.
+    // RP: this lane's box of the stage, box = {lo, hi} (stage_box, sqp_steps.hpp); else the launch's one box
     auto p0_body = [&](int k, float zbar, float yr_in, const float (&trk)[3], float2 lp, const float (&g)[NX],
-                       float bk) __attribute__((always_inline)) {
+                       float bk, float2 box) __attribute__((always_inline)) {
         // stage reference of this lane: run mode unwraps + pads the pose refs (NMPCNavControlDiff.cpp:104-118),
         // entries >= 3 of yref are left at zero
         float yr = yr_in;
@@ -345,12 +350,13 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
             w = vx ? we_lane : w;
         }
         rec[R::GR] = valid ? w * (zbar - yr) : 0.0f;
+        if constexpr (RP) rec[R::GR] = stage_box_poison(rec[R::GR], box, valid && has_b);
         // iterate, bounds, slacks, multipliers
         const float z = vx ? dx : 0.0f;
         rec[R::Z] = z;
         // (sentinels on the slots without a bound, or outside their stage range: bound_start, sqp_steps.hpp)
         {
-            const BoundStart b = bound_start(P, zbar, z, lo_b, hi_b, warm, lp, valid && has_b);
+            const BoundStart b = bound_start(P, zbar, z, RP ? box.x : lo_b, RP ? box.y : hi_b, warm, lp, valid && has_b);
             rec[R::LB] = b.lb;
             rec[R::UB] = b.ub;
             rec[R::TL] = b.tl;
@@ -416,13 +422,18 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         };
         Stg cur, nxt;
         lds_ld(0, cur);
+        // RP: the stage's box from the table, one stage ahead beside the LDS reads (the only global loads of this loop)
+        float2 box = make_float2(lo_b, hi_b), box_n = box;
+        if constexpr (RP) box = stage_box(sbx, 0, N);
         for (int k = 0; k <= N; k++) {
             lds_ld(k + 1, nxt);
+            if constexpr (RP) box_n = stage_box(sbx, k + 1, N);
             float g[NX];
 #pragma unroll
             for (int i = 0; i < NX; i++) g[i] = (i < NGV && k < N) ? cur.g[i < NGV ? i : 0] : 0.0f;
-            p0_body(k, cur.zb, cur.y, cur.t, make_float2(cur.ll, cur.lu), g, cur.b);
+            p0_body(k, cur.zb, cur.y, cur.t, make_float2(cur.ll, cur.lu), g, cur.b, box);
             cur = nxt;
+            box = box_n;
         }
     } else {
         // three row buffers used in turn (the loop unrolled by 3, compile-time buffer indices): buffer i holds stage
@@ -431,11 +442,12 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         // memory operation issued before it (a full drain per stage)
         struct Row {
             float xb[NX], ub[NU], tr[3], yr;
-            float2 lp;
+            float2 lp, bx;  // bx (RP): the lane's box of the stage
         };
         auto load_p0 = [&](int k, Row& o) {
             load_row(k, o.xb, o.ub, o.tr);
             o.lp = load_l(k);
+            if constexpr (RP) o.bx = stage_box(sbx, k, N);
             o.yr = 0.0f;
             if (mode != kModeRun) {  // (unconditional load of a valid entry, then a select)
                 const int kk = k <= N ? k : N;
@@ -454,6 +466,10 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         for (int j = 0; j < 3; j++) { rw[0].tr[j] = tr[j]; rw[1].tr[j] = tr1[j]; }
         rw[0].lp = load_l(0);
         rw[1].lp = load_l(1);
+        if constexpr (RP) {
+            rw[0].bx = stage_box(sbx, 0, N);
+            rw[1].bx = stage_box(sbx, 1, N);
+        }
         rw[0].yr = rw[1].yr = 0.0f;
         if (mode != kModeRun) {
             Row t0, t1;
@@ -486,7 +502,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 #pragma unroll
                 for (int q = 0; q < NX; q++)
                     if (xi == q) bk = xn[q] - n1.xb[q];
-                p0_body(k, zbar, c.yr, c.tr, c.lp, g, bk);
+                p0_body(k, zbar, c.yr, c.tr, c.lp, g, bk, RP ? c.bx : make_float2(lo_b, hi_b));
                 if (k == N) stop = true;
             });
             if (stop) break;
@@ -1116,8 +1132,8 @@ hipError_t launch_sqp_rti_team(const KParams& P, const KArgs& a, int mode, hipSt
             else if (km == kModeRun) go(k_sqp_rti_team<M, ms, sd, kModeRun, sp, rp>);
             else go(k_sqp_rti_team<M, ms, sd, kModeSolve, sp, rp>);
         };
-        // the per-robot table: its own instantiations (sqp_steps.hpp lane_ctx)
-        if (a.rparams) pick3(std::true_type{});
+        // the per-robot table and the stage table: instantiations of their own (sqp_steps.hpp lane_ctx, stage_box)
+        if (a.rparams || a.sbounds) pick3(std::true_type{});
         else pick3(std::false_type{});
     };
     // record layout: tric always split, diff per launch (a.rec_split), omni4 and Mehrotra never

@@ -12,6 +12,7 @@
 //   StageLds         stage inputs in LDS     split launch: P0 part 1 and 2       P0a, P0b, P0c
 //   p0_stage_inputs  zbar, b_k, GV rows      split launch: P0 part 1             P0a `round`
 //   RefUnwrap        reference unwrap + pad  p0_body                             P0b `uw`
+//   stage_box        the lane's box at k     load_p0 (split launch: beside lds_ld) P0c
 //   bound_start      bounds, slacks, lambda  p0_body                             P0c
 //   terminal_weight  the terminal hack       p0_body (stage N)                   before P0c
 //   sqp_full_step    z += dz, x_0 = x0       epilogue                            epilogue
@@ -85,6 +86,51 @@ __device__ __forceinline__ LaneCtx<M> lane_ctx(const KParams& P, const KArgs& a,
     }
     c.h_stage = P.dt * c.w_lane;
     return c;
+}
+
+// ---- this lane's box at a stage (the stage table, KArgs::sbounds) ------------------------------------------------
+// lo / hi: the lane's pair of stage 0, ks: floats from one stage to the next. An input lane points at its lbu / ubu
+// row, a bounded state lane at its lbx / ubx row, every other lane at the robot's first row (a valid dummy, dropped).
+// The table decides the addresses here, once; the loads in P0 are unconditional, as load_l's and RefUnwrap's are, for
+// their reasons (a load under a lane mask, or a value selected behind a branch, turns the waits of P0's loop into full
+// drains). Stage table off and per-robot table on (the team kernel's RP instantiations serve both): the same loads
+// read the robot's column of the per-robot table with ks = 0, so that launch keeps one box for every stage.
+struct StageBox {
+    const float *lo, *hi;
+    size_t ks;
+};
+template <class M>
+__device__ __forceinline__ StageBox stage_box_ctx(const KArgs& a, int inst, const LaneCtx<M>& c, int r)
+{
+    constexpr int NBX = M::NBX, NBU = M::NBU, SR = sb_rows(NBX, NBU);
+    const int bj = c.is_u ? r : (c.cx >= 0 ? c.cx : 0);
+    StageBox s;
+    if (a.sbounds) {
+        const int lo = (c.is_u ? sb_off(kSbLbu, NBX, NBU) : sb_off(kSbLbx, NBX, NBU)) + bj;
+        const int hi = (c.is_u ? sb_off(kSbUbu, NBX, NBU) : sb_off(kSbUbx, NBX, NBU)) + bj;
+        s.lo = a.sbounds + sb_at(0, lo, inst, a.sstride, SR);
+        s.hi = a.sbounds + sb_at(0, hi, inst, a.sstride, SR);
+        s.ks = sb_stage_stride(a.sstride, SR);
+    } else {
+        constexpr RpRows RR = rp_rows(M::NX, M::NU, NBX, NBU);
+        const size_t C = (size_t)a.sstride;
+        s.lo = a.rparams + (size_t)((c.is_u ? RR.off[kRpLbu] : RR.off[kRpLbx]) + bj) * C + inst;
+        s.hi = a.rparams + (size_t)((c.is_u ? RR.off[kRpUbu] : RR.off[kRpUbx]) + bj) * C + inst;
+        s.ks = 0;
+    }
+    return s;
+}
+// {lo, hi} of stage k, k clamped to N (the rows past a field's last used stage are allocated and never interpreted)
+__device__ __forceinline__ float2 stage_box(const StageBox& s, int k, int N)
+{
+    const size_t kk = (size_t)(k <= N ? k : N);
+    return make_float2(s.lo[kk * s.ks], s.hi[kk * s.ks]);
+}
+// fmaxf in bound_start would swallow a NaN bound, so a NaN in a bound the QP uses (bd) poisons that stage's gradient
+// entry gr: the robot then fails alone with status 1, as lane_ctx's NaN weight makes it
+__device__ __forceinline__ float stage_box_poison(float gr, float2 box, bool bd)
+{
+    return (bd && (box.x != box.x || box.y != box.y)) ? __builtin_nanf("") : gr;
 }
 
 // ---- x0 (every lane keeps the full vector) --------------------------------------------------------------------
