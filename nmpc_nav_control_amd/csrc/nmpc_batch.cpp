@@ -68,16 +68,6 @@ struct nmpc_batch {
     // nmpc_kernels.hpp), allocated by the first writer; sb_on: launches read it (resident_args)
     float* sbounds = nullptr;
     bool sb_on = false;
-#ifdef NMPC_HYBRID
-    // hybrid launch (A/B build only, -DNMPC_HYBRID, NMPC_AMD_HYBRID=H): in a team-kernel launch the robots whose last
-    // IPM count was >= H (at most hybrid_cap of them, the hardest first) run the segmented row-parallel kernel (one
-    // wave each) on aux, concurrently with the team kernel on the caller's stream for the rest (measured and not
-    // adopted: metric 4.16 -> 3.84 M it/s at H = 12, DESIGN.md "Hybrid launch")
-    int hybrid_h = 0, hybrid_cap = 1024;
-    int* hyb_n = nullptr;        // [1] robots taken by the segmented part (device)
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-#endif
 };
 
 namespace {
@@ -308,56 +298,15 @@ hipError_t schedule(nmpc_batch* b, KArgs& a, int mode, hipStream_t s)
         return launch_node_order(b->iter_key, b->node_active, a.B, sorted, b->order, b->node_n, s);
     }
     if (a.split) return hipSuccess;  // one robot per wave: nothing to place
-#ifdef NMPC_HYBRID
-    // (the hybrid launch mixes the kernels in one tick: only where they share the record layout)
-    if (b->hybrid_h > 0 && b->kp.ipm == NMPC_IPM_SINGLE && !a.segs && b->hyb_n && p.rec_split == 0) {
-        a.hyb_role = 1;  // launch() adds the segmented part on the aux stream
-        a.hyb_n = b->hyb_n;
-        a.order = b->order;
-        return launch_hybrid_order(b->iter_key, a.B, b->hybrid_h, b->hybrid_cap, b->order, b->hyb_n, s);
-    }
-#endif
     if (layout == NMPC_SCHED_OFF) return hipSuccess;
     a.order = b->order;
     return launch_team_order(b->iter_key, a.B, layout, b->sorted, b->order, s);
 }
 
-#ifdef NMPC_HYBRID
-template <class M>
-hipError_t launch_hybrid(nmpc_batch* b, KArgs& a, int mode, hipStream_t s)
-{
-    // the segmented part: one wave per robot (4 rows, segments per seg_count), ranks [0, hyb_n) of the order
-    KArgs g = a;
-    g.hyb_role = 2;
-    g.hyb_cap = b->hybrid_cap;
-    g.rowpar = 1;
-    g.seg = b->seg >= 0 ? b->seg : seg_count(b->prm.N, 4);
-    if (g.seg > 4 || (g.seg > 0 && b->prm.N % g.seg)) g.seg = 0;
-    if (rowpar_lds_bytes<M>(b->prm.N, mode, g.seg) > 65536) g.seg = 0;
-    hipError_t e;
-    if (!b->aux) {
-        if ((e = hipStreamCreateWithFlags(&b->aux, hipStreamNonBlocking)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming)) != hipSuccess)
-            return e;
-    }
-    if ((e = hipEventRecord(b->ev_fork, s)) != hipSuccess || (e = hipStreamWaitEvent(b->aux, b->ev_fork, 0)) != hipSuccess)
-        return e;
-    if ((e = launch_sqp_rti_rowpar<M>(b->kp, g, mode, b->aux)) != hipSuccess) return e;
-    if ((e = launch_sqp_rti_team<M>(b->kp, a, mode, s)) != hipSuccess) return e;
-    if ((e = hipEventRecord(b->ev_join, b->aux)) != hipSuccess) return e;
-    return hipStreamWaitEvent(s, b->ev_join, 0);
-}
-#endif
-
 hipError_t launch(nmpc_batch* b, KArgs& a, int mode, hipStream_t s)
 {
     const hipError_t e = schedule(b, a, mode, s);
     if (e != hipSuccess) return e;
-#ifdef NMPC_HYBRID
-    if (a.hyb_role == 1)
-        return with_model(b->prm.model, [&](auto m) { return launch_hybrid<decltype(m)>(b, a, mode, s); });
-#endif
     return with_model(b->prm.model, [&](auto m) { return launch_m<decltype(m)>(b, a, mode, s); });
 }
 
@@ -491,11 +440,7 @@ int check_params(const nmpc_model_params* prm)
 extern "C" {
 
 const char* nmpc_last_error(void) { return g_err.c_str(); }
-#ifdef NMPC_HYBRID
-const char* nmpc_version(void) { return "nmpc_amd 0.4 (team-per-instance DPP SQP-RTI, gfx950; A/B: hybrid launch)"; }
-#else
 const char* nmpc_version(void) { return "nmpc_amd 0.4 (team-per-instance DPP SQP-RTI, gfx950)"; }
-#endif
 
 int nmpc_model_dims(int model, int* nx, int* nu, int* ny, int* nbx, int* nbu, int* np)
 {
@@ -618,10 +563,6 @@ int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** o
     if (const char* v = std::getenv("NMPC_AMD_SEG")) b->seg = std::atoi(v);  // A/B: 0 = serial, S = S segments
     if (const char* v = std::getenv("NMPC_AMD_ROWPAR_W")) b->rowpar_w = std::atoi(v) == 1 ? 1 : 2;  // A/B
     if (const char* v = std::getenv("NMPC_AMD_SEG_ROWS")) b->seg_rows = std::atoi(v) == 8 ? 8 : 4;  // A/B
-#ifdef NMPC_HYBRID
-    if (const char* v = std::getenv("NMPC_AMD_HYBRID")) b->hybrid_h = std::atoi(v);  // A/B: 0 = off
-    if (const char* v = std::getenv("NMPC_AMD_HYBRID_CAP")) b->hybrid_cap = std::atoi(v);
-#endif
     const int N = prm->N;
     const size_t S = (size_t)capacity;
     hipError_t e;
@@ -633,12 +574,6 @@ int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** o
         b->n_cu = props.multiProcessorCount;
         if (props.maxSharedMemoryPerMultiProcessor > 0) b->lds_per_cu = props.maxSharedMemoryPerMultiProcessor;
     }
-#ifdef NMPC_HYBRID
-    if ((e = hipMalloc(&b->hyb_n, sizeof(int))) != hipSuccess || (e = hipMemset(b->hyb_n, 0, sizeof(int))) != hipSuccess) {
-        nmpc_batch_destroy(b);
-        return hip_err(e, "hipMalloc");
-    }
-#endif
     if ((e = hipMalloc(&b->iter_key, sizeof(int) * S)) != hipSuccess ||
         (e = hipMalloc(&b->order, sizeof(int) * S)) != hipSuccess ||
         (e = hipMalloc(&b->sorted, sizeof(int) * S)) != hipSuccess ||
@@ -684,12 +619,6 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->node_status);
     (void)hipFree(b->rparams);
     (void)hipFree(b->sbounds);
-#ifdef NMPC_HYBRID
-    (void)hipFree(b->hyb_n);
-    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-    if (b->ev_join) (void)hipEventDestroy(b->ev_join);
-    if (b->aux) (void)hipStreamDestroy(b->aux);
-#endif
     delete b;
     return NMPC_OK;
 }

@@ -83,11 +83,6 @@ struct KArgs {
                     // row k mod 16, joined by a block barrier); small batches
     int seg;        // k_sqp_rti_rowpar: horizon segments S (N % S == 0) whose Riccati sweeps run in parallel on S rows,
                     // joined by a master recursion over the segment boundaries; 0: the serial phases B / C
-    // hybrid launch (A/B build -DNMPC_HYBRID only, nmpc_batch.cpp): the robots of the first hyb_n[0] ranks of `order`
-    // (the hardest by last tick's IPM count) run the segmented row-parallel kernel on a second stream (role 2, at most
-    // hyb_cap blocks), the rest the team kernel (role 1, team slot t -> order[hyb_n[0] + t]); role 0: a plain launch
-    const int* hyb_n;
-    int hyb_role, hyb_cap;
     // one-robot capsule solves (acados_shim.cpp, k_sqp_rti_rowpar only): the kernel copies the capsule's input block
     // from host-mapped memory into the device block at its start and the output block back at its end, in place of a
     // copy launch on each side (stage_in_n / stage_out_n = 0: nothing staged)
@@ -129,8 +124,8 @@ struct RpColumn {
 
 // The stage table: per stage and robot the rows lbx[NBX] ubx[NBX] lbu[NBU] ubu[NBU], (N + 1) stages, `cap` robots.
 // Laid out [stage][robot][row]: one robot's rows of a stage are one cache line (diff, tric 32 B, omni4 64 B), and the
-// lanes of a DPP row read consecutive floats. (-DNMPC_SB_ROW_MAJOR, A/B only: [stage][row][robot], the per-robot
-// table's orientation; profiles/r07/ab/stage_bounds.txt)
+// lanes of a DPP row read consecutive floats. (The per-robot table's orientation, [stage][row][robot], measured level
+// and was removed: profiles/r07/ab/stage_bounds.txt)
 enum SbField { kSbLbx = 0, kSbUbx, kSbLbu, kSbUbu, kSbFields };
 __host__ __device__ constexpr int sb_rows(int nbx, int nbu) { return 2 * nbx + 2 * nbu; }
 __host__ __device__ constexpr int sb_off(int field, int nbx, int nbu)
@@ -140,11 +135,7 @@ __host__ __device__ constexpr int sb_off(int field, int nbx, int nbu)
 // float index of robot i's row `row` at stage k, and the distance from one stage to the next
 __host__ __device__ inline size_t sb_at(int k, int row, int i, int cap, int rows)
 {
-#ifdef NMPC_SB_ROW_MAJOR
-    return ((size_t)k * rows + row) * (size_t)cap + i;
-#else
     return ((size_t)k * cap + i) * (size_t)rows + row;
-#endif
 }
 __host__ __device__ inline size_t sb_stage_stride(int cap, int rows) { return (size_t)cap * rows; }
 
@@ -167,10 +158,6 @@ hipError_t launch_team_order(const int* key, int B, int layout, int* sorted, int
 // others behind them; n_active[0] = their count
 hipError_t launch_node_order(const int* key, const unsigned char* active, int B, int sorted, int* order, int* n_active,
                              hipStream_t stream);
-#ifdef NMPC_HYBRID
-// sorted order (hardest first) plus nhard[0] = min(#robots with key >= H, cap): the hybrid launch's split
-hipError_t launch_hybrid_order(const int* key, int B, int H, int cap, int* order, int* nhard, hipStream_t stream);
-#endif
 // the resident state of the first B robots as nmpc_batch_init_iterate leaves it (mode 0 create, 1 reset), warm flags
 // cleared; launch_forget_warm clears the warm flags alone, of the robots with mask[i] != 0 (nullptr: all)
 hipError_t launch_init_iterate(float* xbar, float* ubar, float* carried, unsigned char* warm, int B, int stride, int N,

@@ -224,10 +224,6 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     constexpr int NX = M::NX, NU = M::NU, NV = R::NV, NGV = R::NGV, RS = R::RS, RSS = R::RSS;
     constexpr bool QM = rec_quad_major<NV>();
     constexpr int ROWS = 4 * W;
-#ifdef NMPC_HYBRID
-    // hybrid launch (A/B build, role 2): block i takes the robot of rank i of the order, for the first hyb_n[0] ranks
-    if (a.hyb_role == 2 && (int)blockIdx.x >= a.hyb_n[0]) return;
-#endif
     // node ticks: block s takes the robot of slot s of the order, for the first *n_active slots (the robots that
     // solve); plain launches (order == nullptr): block i = robot i
     if ((int)blockIdx.x >= a.B || (a.n_active && (int)blockIdx.x >= *a.n_active)) return;
@@ -600,13 +596,6 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
         sum_c0 = v[0];
     }
 
-#ifdef NMPC_ROWPAR_MCOL
-    // A/B only: the column-form M block needs about 20 more registers, which pushes the segmented kernels past the
-    // 256 that two waves per SIMD allow (tests/test_reg_usage.py), so the row form stays; tests/test_codegen.py
-    // compiles this variant so that it keeps building
-    GConst<M> gcs;  // the constant rows of [B A] as uniform operands of the M block (m_block)
-    gconst_load<M>(gcs, gcol);
-#endif
     const int m = N * NU + N * M::NBX;
     const float inv_m2 = 0.5f / (float)m;
 
@@ -958,14 +947,9 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
 #pragma unroll
                     for (int jj = 0; jj < NV; jj++) Lr[jj] = (r == jj) ? dg : 0.0;
                     double pivot;
-#ifdef NMPC_ROWPAR_MCOL
-                    double m11, m10;  // the 2x2 input block for up-front pivots (unused: pivots in turn below)
-                    m_block<M>(Lr, pivot, m11, m10, pg, Gd, gcs);
-                    (void)m11;
-                    (void)m10;
-#else
+                    // (the row form: the team kernel's column form needs about 20 more registers, past the 256 that
+                    // two waves per SIMD allow the segmented kernels, tests/test_reg_usage.py)
                     mrow_pg_block<NX, NU>(Lr, pivot, pg, Gd);
-#endif
                     sfor<0, NU>([&](auto jc) {
                         constexpr int j2 = decltype(jc)::value;
                         if (!(pivot > 0.0) && srow) fail = true;
@@ -1106,14 +1090,9 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
             // D = -Gam_i, F = Phi_i'), so they cost one step's issue; on two waves of a CU they slowed each other
             // down by half (profiles/r05/stamps/). Every Q (Q_i, Q'_i, Q_j) is A (I + C A)^-1 = L (I + L' C L)^-1 L'
             // with C >= 0 (mst_qform). Lane NU + r of a row holds row r of every matrix and element r of every vector.
-#ifdef NMPC_SEQ_MASTER
-            constexpr bool kSeqM = true;  // A/B only: the round-4 master (backward over all S - 1 boundaries, then forward)
-#else
-            constexpr bool kSeqM = false;
-#endif
-            const int mj = kSeqM ? 0 : Sg / 2;        // the join boundary (1 <= m <= S - 1)
+            const int mj = Sg / 2;                    // the join boundary (1 <= m <= S - 1)
             const int nbw = Sg - 1 - mj;              // backward-sweep steps (boundaries S - 2 .. m)
-            const int ndu = kSeqM ? 0 : mj - 1;       // dual-sweep steps (boundaries 1 .. m - 1)
+            const int ndu = mj - 1;                   // dual-sweep steps (boundaries 1 .. m - 1)
             const bool mrow0 = tid < 16;              // backward sweep, join, forward propagation
             const bool bwr = mrow0;                   // (row 1 of wave 0: the dual side)
             float* const sl = seg_lds + SegL.SL;
@@ -1185,7 +1164,7 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
                 RP_MSTAMP(1, 0);
                 // the join (row 0): lam_m, s_m
                 double sv = 0.0, lam_m = 0.0;
-                if (!kSeqM && bwr) {
+                if (bwr) {
                     double Pm[NX], Sr[NX], Q[NX];
 #pragma unroll
                     for (int c = 0; c < NX; c++) {
@@ -1208,8 +1187,8 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
                 // outward propagation, both rows as one stream: z = s_i (row 0, i = m .. S - 2) / lam_{i+1} (row 1,
                 // i = m - 1 .. 1);  y = F z (F = Phi_i' / Phi_i);  o = b0 + sO Q_i (y + alpha) (lam_{i+1} / s_i);
                 // z' = y + beta + R o (s_{i+1} / lam_i), R = Gam_i / P_i
-                double z = bwr ? sv : (kSeqM ? 0.0 : sXa[2 * (NX + 1) * NX + xi]);
-                const int nfw = Sg - 1 - mj, nbp = kSeqM ? 0 : mj - 1;
+                double z = bwr ? sv : sXa[2 * (NX + 1) * NX + xi];
+                const int nfw = Sg - 1 - mj, nbp = mj - 1;
                 const int no = nfw > nbp ? nfw : nbp;
                 const int gs1 = bwr ? 1 : NX, gs2 = bwr ? NX : 1;  // (the transposed F of the sweep)
                 for (int j = 0; j < no; j++) {
@@ -1402,14 +1381,7 @@ __global__ __launch_bounds__(64 * W, (SEG && M::NX < 10 && W <= kRowparW2Max) ? 
     #pragma unroll
                         for (int j = 0; j < NV; j++) Lr[j] = (r == j) ? dg : 0.0;
                         double pivot;
-#ifdef NMPC_ROWPAR_MCOL
-                        double m11, m10;  // unused: pivots in turn below
-                        m_block<M>(Lr, pivot, m11, m10, pg, Gd, gcs);
-                        (void)m11;
-                        (void)m10;
-#else
                         mrow_pg_block<NX, NU>(Lr, pivot, pg, Gd);
-#endif
                         sfor<0, NU>([&](auto jc) {
                             constexpr int j = decltype(jc)::value;
                             if (!(pivot > 0.0)) fail = true;
@@ -1632,11 +1604,7 @@ hipError_t launch_sqp_rti_rowpar(const KParams& P, const KArgs& a, int mode, hip
     const int W = a.rowpar >= 4 ? 4 : (a.rowpar == 2 ? 2 : 1);
     if (a.seg < 0 || a.seg > kSegMax || a.seg > 4 * W || (a.seg > 0 && P.N % a.seg != 0))
         return hipErrorInvalidValue;
-#ifdef NMPC_HYBRID
-    const int grid = (a.hyb_role == 2) ? (a.B < a.hyb_cap ? a.B : a.hyb_cap) : a.B;
-#else
     const int grid = a.B;
-#endif
     // (a block above 64 KiB of LDS -- a long horizon on four waves, or omni4's wider stage fields -- asks for it)
     auto go = [&](auto kern, int threads) {
         if (lds > 65536) {

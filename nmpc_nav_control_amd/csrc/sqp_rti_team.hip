@@ -117,19 +117,13 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     const int team = a.split ? (int)blockIdx.x : (gt >> 4);
     const int row = a.split ? (int)(threadIdx.x >> 4) : 0;
     const int r = gt & 15;
-#ifdef NMPC_HYBRID
-    // hybrid launch (A/B build): the first hyb_n[0] ranks of the order run the segmented kernel on another stream
-    const int hoff = (a.hyb_role == 1) ? a.hyb_n[0] : 0;
-#else
-    constexpr int hoff = 0;
-#endif
-    if (team >= a.B - hoff) return;  // whole DPP rows leave together
+    if (team >= a.B) return;  // whole DPP rows leave together
     // node ticks: the robots that solve fill the first *n_active slots of the order; the other slots leave
     if (a.n_active && team >= *a.n_active) return;
     const int N = P.N;
     const size_t S = (size_t)a.stride;  // resident state stride (capacity)
     const size_t Bn = (size_t)a.B;
-    const int inst = a.order ? a.order[hoff + team] : team;  // difficulty-ordered placement (schedule.hip)
+    const int inst = a.order ? a.order[team] : team;  // difficulty-ordered placement (schedule.hip)
     // this lane's roles, stage weight and box (sqp_steps.hpp)
     const LaneCtx<M> lc = lane_ctx<M, RP>(P, a, inst, r);
     const bool lv = lc.lv, is_u = lc.is_u, is_x = lc.is_x, has_b = lc.has_b;
@@ -370,19 +364,15 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         // 15-slot teams (omni4): unconditional (the idle lane stores zeros / sentinels into its own unused
         // slot). A store under a lane mask may or may not be issued, so the compiler's waits for the next loads
         // drain the whole memory counter, these stores included. Same-box A/B: omni4 kernel 1.303 -> 1.256 ms;
-        // diff (7 idle lanes, +78 % P0 store bytes) 1.043 -> 1.065 ms, so 9-slot teams keep the masked store
+        // diff (7 idle lanes, +78 % P0 store bytes) 1.043 -> 1.065 ms, so 9-slot teams do not store per idle lane
         // (profiles/r02/ab/uncond_stores.txt)
         if constexpr (NV > 12) rec_store_range<0, RSS, RS, QM>(tbase_own + (size_t)k * KS, rec);
-#ifdef P0_MASKED_STORE
-        else if (lv) rec_store_range<0, RSS, RS, QM>(tbase + (size_t)k * KS, rec);
-#else
         // 9-slot teams: the idle lanes all store into the team's dummy record (one record's bytes, not seven)
         else if constexpr (SPL)
             split_store<R, 0, R::GR + 1, RS>(lv ? pc0 + (size_t)k * R::CS : tdummy,
                                              (lv && has_b) ? pb0 + (size_t)k * kb : tdummy + R::CW, rec);
         else rec_store_range<0, RSS, RS, QM>(lv ? tbase + (size_t)k * KS : tdummy, rec);
-#endif
-        if constexpr (kDzPlane) dzbase[(size_t)k * 16] = 0.0f;  // P1 of iteration 0 applies a zero step
+        dzbase[(size_t)k * 16] = 0.0f;  // P1 of iteration 0 applies a zero step
         // dynamics-feasible initial states: dx_{k+1} = A dx_k + b_k (inputs start at du = 0, dx_0 = x0 - xbar_0);
         // row i of [B A] dz: NGV row sums over the columns + the constant rows held in grow
         if (k < N) {
@@ -517,29 +507,12 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 #pragma unroll
     for (int i = 0; i < NX; i++) gcol64[i] = (double)gcol[i];
 #ifdef NMPC_MROW
-    constexpr bool kMcol = false;  // A/B: the row form for every model
-#elif defined(NMPC_MCOL_ALL)
-    constexpr bool kMcol = true;  // A/B: the column form for every model
+    constexpr bool kMcol = false;  // checker build (lib/mrow): the row form for every model
 #else
     constexpr bool kMcol = M::kMcolForm;  // per model (nmpc_models.hpp)
 #endif
-    // -DNMPC_F32_FACTOR (A/B build): the single-direction rule factors in fp32 with the bounded states' barrier
-    // weights split off (team_common.hpp chol_split_f32). As accurate as the fp64 factor (same IPM counts in the
-    // closed loop, every full-batch replay green) but slower on every config, 3-10 % (profiles/r06/ab/fp32_factor.txt,
-    // DESIGN.md section 5), so the product keeps the fp64 factorisation
-#ifdef NMPC_F32_FACTOR
-    constexpr bool kF32 = SD && kMcol;
-#else
-    constexpr bool kF32 = false;
-#endif
-    using FT = std::conditional_t<kF32, float, double>;
     GConst<M> gcs;  // the constant rows of [B A] as uniform operands of the column-form M block (m_block)
-    GConstF<M> gcf;  // the same in fp32 (m_block_f32, chol_split_f32)
-    if constexpr (kF32) gconst_load_f<M>(gcf, gcol);
-    else if constexpr (kMcol) gconst_load<M>(gcs, gcol);
-    // fp32 factor: a bounded state's barrier weight stays out of P_k (lane NU + idxbx(c), c = cx); s_next carries it
-    // from stage k's body to stage k - 1's pivot of input c
-    const bool split_lane = kF32 && is_x && cx >= 0;
+    if constexpr (kMcol) gconst_load<M>(gcs, gcol);
 
     STAMP(1);
     // infeasibility threshold of this robot: qp_infeas_lambda scaled by its largest weight (terminal hack included)
@@ -560,7 +533,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     auto p1_load = [&](int kk, float (&v)[RS]) {
         if constexpr (SPL) split_load<R, R::P1L0, R::P1L1, RS>(pc0 + (size_t)kk * R::CS, pb0 + (size_t)kk * kb, v);
         else rec_load_range<R::P1L0, R::P1L1, RS, QM>(tbase + (size_t)kk * KS, v);
-        if constexpr (kDzPlane) v[R::DZ] = dzbase[(size_t)kk * 16];
+        v[R::DZ] = dzbase[(size_t)kk * 16];
     };
     auto sweep = [&](int k0, int k1, int dir, bool ld, auto&& body) {  // 2 buffers (compute-heavy P1)
         const int sd = ld ? dir : 0;  // stage step of this lane's loads (0: a lane that does not sweep)
@@ -592,7 +565,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         auto load = [&](int kk, float (&v)[RS]) {
             if constexpr (SPL) split_load<R, F0, F, RS>(pc0 + (size_t)kk * R::CS, pb0 + (size_t)kk * kb, v);
             else rec_load_range<F0, F, RS, QM>(tbase + (size_t)kk * KS, v);
-            if constexpr (kDzPlane && F == R::P1L1) v[R::DZ] = dzbase[(size_t)kk * 16];
+            if constexpr (F == R::P1L1) v[R::DZ] = dzbase[(size_t)kk * 16];
         };
         load(kp, buf[0]);
         sfor<1, D>([&](auto ic) {
@@ -629,10 +602,9 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     for (int it = 0;; it++) {
         // P1 (backward): apply the previous step, residuals, adjoint, fp64 classic Riccati factorisation,
         // predictor rhs
-        FT Lrow[NV];  // lane NU+i: row i of P_{k+1} (the state block of the previous stage's M after its pivots)
+        double Lrow[NV];  // lane NU+i: row i of P_{k+1} (the state block of the previous stage's M after its pivots)
 #pragma unroll
         for (int j = 0; j < NV; j++) Lrow[j] = 0.0;
-        float s_next = 0.0f;  // fp32 factor: the split lane's barrier weight of stage k + 1 (0 elsewhere)
         float pv = 0.0f, piv = 0.0f;
         float res_stat = 0.0f, res_ineq = 0.0f, sum_c = 0.0f, max_c = 0.0f, stat_scale = 1.0f, nanf_ = 0.0f;
         float lam_max = 0.0f;
@@ -706,47 +678,11 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
             const float pi_new = vx ? base : 0.0f;
             if (ghat != ghat || sig != sig) nanf_ = 1.0f;
             if (k == N) {
-                // terminal: P_N = diag(W_e + Sigma) on the state lanes (fp32 factor: Sigma of a bounded state in
-                // s_next instead)
-                const FT d = is_x ? (FT)fmaxf(we_lane + (split_lane ? 0.0f : sig), 0.0f) : (FT)0.0;
+                // terminal: P_N = diag(W_e + Sigma) on the state lanes
+                const double d = is_x ? (double)fmaxf(we_lane + sig, 0.0f) : 0.0;
 #pragma unroll
-                for (int j = 0; j < NV; j++) Lrow[j] = (is_x && j == r) ? d : (FT)0.0;
-                s_next = split_lane ? sig : 0.0f;
+                for (int j = 0; j < NV; j++) Lrow[j] = (is_x && j == r) ? d : 0.0;
                 pv = is_x ? ghat : 0.0f;
-            } else if constexpr (kF32) {
-                // fp32 split-sigma factorisation: M~ = D~ + G' P~ G with the bounded states' barrier weights out of
-                // D~ and P~ (team_common.hpp chol_split_f32 enters those of stage k + 1 at their inputs' pivots)
-                float pg[NX];
-#pragma unroll
-                for (int i = 0; i < NX; i++) pg[i] = 0.0f;
-                STAMPF(2);
-                pg_block_f<NX, NU>(pg, Lrow, Gc);
-                STAMPF(3);
-                const float dg = valid ? h_stage + (split_lane ? 0.0f : sig) : 1.0f;
-                float Lr[NV];
-#pragma unroll
-                for (int j = 0; j < NV; j++) Lr[j] = (j == r) ? dg : 0.0f;
-                float pivot;  // = M[0][0]
-                m_block_f<M>(Lr, pivot, pg, Gc, gcf);
-                STAMPF(4);
-                chol_split_f32<M>(Lr, pivot, s_next, gcf, r, fail);
-                s_next = (split_lane && vx) ? sig : 0.0f;
-                STAMPF(5);
-#pragma unroll
-                for (int q = 0; q < NU; q++) rc[R::LM + q] = Lr[q];
-                // rhs: w = g^ + G' p_{k+1}; forward substitution over the input block (fp32)
-                float y = dot_x<NX, NU>(ghat, pv, Gc);
-                float my_lr = 0.0f;
-                sfor<0, NU>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value;
-                    const float lrj = bc<j>(y * frcp(Lr[j]));  // (y_j / L_jj) from lane j
-                    if (r == j) my_lr = lrj;
-                    y -= Lr[j] * lrj;
-                });
-                rc[R::LR] = my_lr;
-                pv = is_x ? y : 0.0f;
-#pragma unroll
-                for (int j = 0; j < NV; j++) Lrow[j] = Lr[j];
             } else {
                 double Gd[NX];
 #pragma unroll
@@ -771,12 +707,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                     double m11, m10;
                     m_block<M>(Lr, pivot, m11, m10, pg, Gd, gcs);  // column form: uniform constant rows + 3 broadcast rows
                     STAMPF(4);
-#ifdef NMPC_SEQ_PIVOTS
-                    constexpr bool kPiv2 = false;  // A/B: the pivots one after the other for every model
-#else
-                    constexpr bool kPiv2 = M::kPivotsUpFront;
-#endif
-                    if constexpr (NU == 2 && kPiv2) {
+                    if constexpr (NU == 2 && M::kPivotsUpFront) {
                         chol_input_2<NX>(Lr, pivot, m11, m10, r, fail);  // both pivots up front
                         seq_pivots = false;
                     } else {
@@ -786,13 +717,6 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                 } else {
                     mrow_pg_block<NX, NU>(Lr, pivot, pg, Gd);  // the row form (NX x NV broadcast FMAs)
                     STAMPF(4);
-#ifdef NMPC_ROW_PIV2
-                    if constexpr (NU == 2) {  // A/B: both input pivots up front with the row form too
-                        const double m11 = bc64<1>(Lr[1]), m10 = bc64<1>(Lr[0]);
-                        chol_input_2<NX>(Lr, pivot, m11, m10, r, fail);
-                        seq_pivots = false;
-                    }
-#endif
                 }
                 if (seq_pivots) sfor<0, NU>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
@@ -826,7 +750,6 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
             }
             piv = pi_new;
             STAMPF(6);
-#ifndef P1_MASKED_STORE
             // Unconditional stores: lanes without work (idle slots, finished teams) write a record nobody reads.
             // Under a lane mask the stores sit in a branch the wave may skip, and the compiler then placed an
             // s_waitcnt vmcnt(0) at the loop header of the ping-pong sweep (it waited for the stores just issued
@@ -844,17 +767,6 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
             } else {
                 rec_store_range<0, R::P1S1, RS, QM>(pk, rc);
             }
-#else
-            if constexpr (MS) {
-                if (act && bnd) rec_store_range<R::TL, R::TL + 4, RS, QM>(tbase + (size_t)k * KS, rc);
-                if (act) {
-                    if constexpr (R::TL > 0) rec_store_range<0, R::TL, RS, QM>(tbase + (size_t)k * KS, rc);
-                    if constexpr (R::TL + 4 < R::P1S1) rec_store_range<R::TL + 4, R::P1S1, RS, QM>(tbase + (size_t)k * KS, rc);
-                }
-            } else {
-                if (act) rec_store_range<0, R::P1S1, RS, QM>(tbase + (size_t)k * KS, rc);
-            }
-#endif
             STAMPF(7);
         });
         if (it < kStampItsC) STAMP(2 + 4 * it);
@@ -1034,9 +946,9 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                 {  // unconditional (lanes without a direction write the dummy record): a masked store here left
                    // the compiler's wait after the sweep a full drain
                     const bool st = ld && valid;
-                    if (corr && kDzPlane) *(st ? dzbase + (size_t)k * 16 : tdummy) = dz;
-                    else *((st && !SPL) ? tbase + (size_t)k * KS + (!corr ? rec_off<RS, QM>(R::DZA) : rec_off<RS, QM>(R::DZ))
-                              : tdummy) = dz;  // (split records: single-direction only, DZ in the plane)
+                    if (corr) *(st ? dzbase + (size_t)k * 16 : tdummy) = dz;
+                    else  // (the affine direction; split records are single-direction only and have none)
+                        *((st && !SPL) ? tbase + (size_t)k * KS + rec_off<RS, QM>(R::DZA) : tdummy) = dz;
                 }
                 if (k < N) dxs = stage_dyn<M, R::GV>(lc, rc, valid ? dz : 0.0f, grow);
             });

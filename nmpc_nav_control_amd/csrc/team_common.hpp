@@ -9,12 +9,6 @@
 
 namespace nmpc {
 
-#ifndef NMPC_DZ_IN_RECORD
-constexpr bool kDzPlane = true;
-#else
-constexpr bool kDzPlane = false;  // A/B: the round-2 layout, DZ a field of the lane record
-#endif
-
 constexpr bool rec_quad_major_v(int nv) { return nv > 12; }
 
 template <class M, bool SD = false>
@@ -38,14 +32,14 @@ struct TeamRec {
     static constexpr int LB = L2 ? 8 : ((NU == 2) ? 9 : 12), UB = LB + 1;  // bounds relative to the SQP iterate
     static constexpr int GV = L2 ? 10 : ((NU == 2) ? 12 : 14);      // NGV varying rows of column v of [B A]
     static constexpr int NL = GV + NGV;                             // prefix read by the light sweeps
-    // combined direction, cost gradient (P1 only). DZ plane (default): the forward sweep writes one float per lane
-    // and stage; in the lane record that dirtied a whole 32-byte sector per lane (8x the bytes), so DZ lives in a
-    // dense plane [robot][stage][16 lanes] (64 B per team and stage, 2 sectors for 9 lanes) and its register slot
-    // sits past the record's stored fields
-    static constexpr int GR = kDzPlane ? NL : NL + 1;
+    // cost gradient, combined direction (P1 only). The forward sweep writes one DZ float per lane and stage; in the
+    // lane record that dirtied a whole 32-byte sector per lane (8x the bytes), so DZ lives in a dense plane
+    // [robot][stage][16 lanes] (64 B per team and stage, 2 sectors for 9 lanes) and its register slot sits past the
+    // record's stored fields
+    static constexpr int GR = NL;
     static constexpr int RU = L2 ? GR + 1 : LM + NU;                // u residual (corrector sweeps)
     static constexpr int DZA = L2 ? GR + 2 : Z + 1 + ((NU == 2) ? 2 : 0);  // affine direction
-    static constexpr int DZ = kDzPlane ? (L2 ? GR + 3 : GR + 1) : NL;
+    static constexpr int DZ = L2 ? GR + 3 : GR + 1;
     static constexpr int P1L0 = L2 ? Z : ((NU == 2) ? TL : Z), P1L1 = GR + 1;  // P1 loads
     static constexpr int P1S1 = L2 ? 8 : 12;                        // P1 stores [0, P1S1)
     static_assert(NU == 2 || NU == 4, "layouts for NU = 2 and 4");
@@ -57,17 +51,15 @@ struct TeamRec {
     // stored floats per lane record: fields [0, GR] (every kernel stores nothing past the gradient; the register
     // image may hold more: the DZ slot of the DZ plane and, in the single-direction layout, the corrector-only RU /
     // DZA). tric (NGV = 3): 16 stored against a 20-float image, 64-B instead of 80-B records
-#ifndef NMPC_RSS_FULL
     static constexpr int RSS = (GR + 1 + 3) / 4 * 4;
-#else
-    static constexpr int RSS = RS;  // A/B: the round-3 stride (records as long as the register image)
-#endif
     static constexpr int NQ = RS / 4;
     static_assert(NV <= 16, "a team holds at most 16 variables");
     static_assert(TL % 4 == 0, "bound quad aligned");
-    static_assert(RSS <= RS && (kDzPlane || DZ < RSS) && (L2 || (RU < RSS && DZA < RSS)), "stored fields");
-    // Split records (team kernel, single-direction layout of tric; NMPC_REC_FULL: the 64-B stage blocks for A/B): per robot a core plane [stage][NV slots][8] = LR LM[2] Z | GV[NGV] GR (pad) and a bound
-    // plane [stage][NBND bounded slots][8] = TL TU LL LU | LB UB (pad), in the robot's old record region. A slot
+    static_assert(RSS <= RS && (L2 || (RU < RSS && DZA < RSS)), "stored fields");
+    // Split records (team kernel, single-direction layout of diff and tric; -DNMPC_REC_FULL: the 64-B stage blocks
+    // for every model, for A/B runs): per robot a core plane
+    // [stage][NV slots][8] = LR LM[2] Z | GV[NGV] GR (pad) and a bound plane
+    // [stage][NBND bounded slots][8] = TL TU LL LU | LB UB (pad), in the robot's old record region. A slot
     // without a bound keeps no bound fields in memory: its loads read the sentinel quad pair (kFar slacks and
     // bounds, zero multipliers) and its stores go to the robot's dummy pair. A sweep's stage then touches
     // 9 x 32 B of core plane (2.25 lines, stages contiguous) + 128 B of bound plane instead of 5 lines of 64-B
@@ -91,8 +83,7 @@ struct TeamRec {
     static constexpr int BS = NBND * CW;         // bound floats per stage
     static_assert(!SPLIT_OK || (TL == 4 && LB == 8 && GV == 10 && GR == GV + NGV && NGV <= 3), "split record map");
     static_assert(!SPLIT_OK || (CS + BS) <= 16 * RSS, "split planes fit the robot's record region");
-    // split planes keep no DZ / DZA field: the forward sweep's direction must live in the DZ plane
-    static_assert(!SPLIT_OK || kDzPlane, "split record planes need the DZ plane (NMPC_DZ_IN_RECORD off)");
+    // (split planes keep no DZ / DZA field: the forward sweep's direction lives in the DZ plane)
 };
 
 namespace {
@@ -180,104 +171,6 @@ __device__ __forceinline__ void m_block(double (&Lr)[M::NX + M::NU], double& piv
         mcol_var_block_11_4_3(Lr, pivot, pg, gd);
         m11 = m10 = 0.0;
     }
-}
-
-// ---- fp32 split-sigma factorisation (single-direction team kernel) ---------------------------
-// The fp64 factor above exists because a bounded state's barrier weight s (up to ~1e12 near the solution) enters
-// P_{k+1} and cancels in the Schur complement P_k = Qxx - Qxu Quu^-1 Qux, which fp32 cannot hold. Every bounded state
-// of the three models is a reference integrator: row idxbx(c) of [B A] is g = h e_{u_c} + gam e_{x_idxbx(c)} (h = dt,
-// gam = 1; static_assert below), so s enters stage k as s g g'. Kept out of P (P = P~ + sum_c s_c e e'), it is added
-// at the pivot of input c -- the pivot gets h^2 s, entry (x, u_c) h gam s -- and the one Schur update that cancels s,
-// the diagonal (x, x), is evaluated in closed form from the s-free entries a = M[c][c], b = M[x][c], e = M[x][x]:
-//     e + gam^2 s - (b + h gam s)^2 / (a + h^2 s) = [s (gam^2 a - 2 h gam b + h^2 e) + (a e - b^2)] / (a + h^2 s)
-// (exact algebra, no s - s). tools/fp32_factor_study.py (variant splitsig) on 12288 dumped metric QPs:
-// profiles/r06/ab/fp32_factor_study_metric.txt; the same recursion fully in fp32 leaves u0 errors up to 1.2e-3.
-template <class M>
-struct GConstF {
-    float v[M::NX][M::NX + M::NU];
-};
-template <class M>
-__device__ __forceinline__ void gconst_load_f(GConstF<M>& gc, const float (&gcol)[M::NX])
-{
-    constexpr int NX = M::NX, NV = M::NX + M::NU;
-    sfor<mcol_nbc<M>(), NX>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        sfor<0, NV>([&](auto rc) {
-            constexpr int r = decltype(rc)::value;
-            if constexpr ((M::gmask(i) >> r) & 1u)
-                gc.v[i][r] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gcol[i]), r));
-            else
-                gc.v[i][r] = 0.0f;
-        });
-    });
-}
-template <int NX, int NU>
-__device__ __forceinline__ void pg_block_f(float (&acc)[NX], const float (&prow)[NX + NU], const float (&gd)[NX])
-{
-    if constexpr (NX == 7 && NU == 2) pg_block_f32_7_2(acc, prow, gd);
-    else pg_block_f32_11_4(acc, prow, gd);
-}
-// m_block in fp32 (column form; pivot = M[0][0])
-template <class M>
-__device__ __forceinline__ void m_block_f(float (&Lr)[M::NX + M::NU], float& pivot, const float (&pg)[M::NX],
-                                          const float (&gd)[M::NX], const GConstF<M>& gc)
-{
-    constexpr int NX = M::NX, NU = M::NU, NV = NX + NU;
-    static_assert(mcol_nbc<M>() == 3, "generated broadcast blocks cover three rows");
-    sfor<mcol_nbc<M>(), NX>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        sfor<0, NV>([&](auto rc) {
-            constexpr int r = decltype(rc)::value;
-            if constexpr ((M::gmask(i) >> r) & 1u) Lr[r] = __builtin_fmaf(gc.v[i][r], pg[i], Lr[r]);
-        });
-    });
-    if constexpr (NX == 7 && NU == 2) mcol_var_block_f32_7_2_3(Lr, pivot, pg, gd);
-    else mcol_var_block_f32_11_4_3(Lr, pivot, pg, gd);
-}
-template <int NX, int NU, int J>
-__device__ __forceinline__ void chol_update_f(float (&lr)[NX + NU], float lj, float& piv)
-{
-    if constexpr (NX == 7 && NU == 2) chol_update_f32_7_2<J>(lr, lj, piv);
-    else chol_update_f32_11_4<J>(lr, lj, piv);
-}
-// The input pivots of M = M~ + sum_c s_c g_c g_c' (row-distributed, lane r holds row r of M~ in Lr; pivot = M~[0][0]
-// broadcast), pivots in turn. s_own: the barrier weight s_c of x_{k+1, idxbx(c)} on that state's lane (0 elsewhere).
-// Leaves the input columns of the factor in Lr[0..NU) and the Schur complement P~_k in the state block. fail: a
-// pivot <= 0 (or NaN).
-template <class M>
-__device__ __forceinline__ void chol_split_f32(float (&Lr)[M::NX + M::NU], float pivot, float s_own,
-                                               const GConstF<M>& gc, int r, bool& fail)
-{
-    constexpr int NX = M::NX, NU = M::NU;
-    sfor<0, NU>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        constexpr bool kB = j < M::NBX;
-        constexpr int ib = kB ? M::idxbx(j) : 0;  // the state input j drives
-        constexpr int xl = NU + ib;                // its lane
-        static_assert(!kB || M::gmask(ib) == ((1u << j) | (1u << xl)), "bounded state = integrator of its input");
-        float s = 0.0f, h = 0.0f, gam = 0.0f, a = 0.0f, b = 0.0f, e = 0.0f;
-        if constexpr (kB) {
-            h = gc.v[ib][j];
-            gam = gc.v[ib][xl];
-            s = bc<xl>(s_own);
-            a = pivot;  // s-free entries (after the previous pivots' updates)
-            b = Lr[j];  // lane xl: M[xl][j]
-            e = Lr[xl]; // lane xl: M[xl][xl]
-            const float hs = h * s;
-            pivot = __builtin_fmaf(h, hs, pivot);
-            Lr[j] += (r == j) ? h * hs : ((r == xl) ? gam * hs : 0.0f);
-        }
-        if (!(pivot > 0.0f)) fail = true;
-        const float rd = __builtin_amdgcn_rsqf(fmaxf(pivot, 1e-30f));
-        const float lj = (r >= j) ? Lr[j] * rd : 0.0f;
-        Lr[j] = lj;
-        chol_update_f<NX, NU, j>(Lr, lj, pivot);
-        if constexpr (kB) {
-            const float num = __builtin_fmaf(s, gam * gam * a - 2.0f * h * gam * b + h * h * e, a * e - b * b);
-            const float den = __builtin_fmaf(h * h, s, a);
-            if (r == xl) Lr[xl] = num * frcp(den);
-        }
-    });
 }
 
 // Right-looking Cholesky of a 2 x 2 input block held row-wise (lane r: Lr = row r of M, m00 / m11 / m10 its
