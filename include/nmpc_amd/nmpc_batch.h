@@ -134,7 +134,11 @@ int nmpc_batch_solve_iterate(nmpc_batch* b, int B, const float* x0, const float*
  * (NMPCNavControlDiff.cpp:168-172). A robot whose solve fails (status != 0) gets a zero (stop) cmd, keeps its
  * carried refs and its iterate: the reference throws there and the node publishes a stop command
  * (NMPCNavControl.cpp:14-23, NMPCNavControlROS.cpp:716-719). Failures stay on their robot: a NaN robot exits
- * its IPM at the first iteration and no other robot's arithmetic depends on it. */
+ * its IPM at the first iteration and no other robot's arithmetic depends on it.
+ * The unwrap decision (|delta| > pi) and the terminal-weight hack's equality test are taken in fp32 on the fp32
+ * inputs. A heading step within one fp32 ulp of pi may therefore unwrap the other way than the fp64 reference would
+ * (e.g. from pose theta = 0 to a reference theta = (float)pi), and two references that differ by less than an fp32
+ * ulp at magnitude 2 pi may compare equal after the unwrap; both outcomes are valid headings. */
 int nmpc_batch_run(nmpc_batch* b, int B, const float* pose, const float* vel, const float* steer,
                    const float* traj, const int* traj_len, const unsigned char* reset, float* cmd, float* u0,
                    int* status, int* qp_iter, float* qp_res, void* stream);
