@@ -97,7 +97,8 @@ int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** o
 int nmpc_batch_destroy(nmpc_batch* b);
 /* Replace weights / bounds / parameters / QP options (model and N must not change). While the per-robot table is
  * on (nmpc_batch_set_robot_params below), lbx, ubx, lbu, ubu, W and W_e do not reach a launch; while the stage table
- * is on (nmpc_batch_set_stage_bounds below), the four bound fields do not. */
+ * is on (nmpc_batch_set_stage_bounds below), the four bound fields do not; while the model table is on
+ * (nmpc_batch_set_robot_model below), p does not. */
 int nmpc_batch_set_params(nmpc_batch* b, const nmpc_model_params* prm);
 int nmpc_batch_get_params(const nmpc_batch* b, nmpc_model_params* prm);
 /* Re-initialise instances [0, B): mode 0 = create semantics (x = [0,0,pi,0,...], u = 0, carried ref states 0);
@@ -398,10 +399,10 @@ int nmpc_batch_warm_state(nmpc_batch* b, unsigned char** warm, float** scratch, 
  *     a nonzero status through the solver's existing exits (status 4: infeasible QP or iteration limit); no other
  *     robot is affected, and the robot keeps its iterate and carried refs and gets a stop command, as after any
  *     failed solve. The input weights R must stay > 0, as nmpc_batch_create requires of the handle's.
- *   - Two scopes stay with the handle: the model parameters p (b, tau_v, ...), which the kernels take as uniform
- *     operands (the constant rows of the stage Jacobian are shared by the robots of a wave), and weights that vary
- *     along the horizon (one W per robot, for every stage). Bounds that vary along the horizon have a table of their
- *     own (nmpc_batch_set_stage_bounds below), which then replaces this table's four bound rows.
+ *   - One scope stays with the handle: weights that vary along the horizon (one W per robot, for every stage).
+ *     Bounds that vary along the horizon have a table of their own (nmpc_batch_set_stage_bounds below), which then
+ *     replaces this table's four bound rows, and the model parameters p (b, tau_v, ...) have one too
+ *     (nmpc_batch_set_robot_model below).
  * Argument errors (NMPC_ERR_ARG): B out of range, rp NULL, every field NULL (nmpc_batch_set_robot_limits: every
  * array NULL), a NULL handle. */
 typedef struct nmpc_robot_params {
@@ -458,8 +459,7 @@ int nmpc_batch_clear_robot_params(nmpc_batch* b);
  *     the plant only when dt_ctrl == dt, which holds for the defaults (both 1/40); otherwise upload the profile
  *     again, sampled at the solver's stage times.
  *   - Still with the handle: stage-varying weights (the stage weight is read inside every IPM iteration, so a weight
- *     per stage would cost the hot loop), the model parameters p, and the capsule ABI, which keeps rejecting
- *     stage-varying data.
+ *     per stage would cost the hot loop), and the capsule ABI, which keeps rejecting stage-varying data.
  * Argument errors (NMPC_ERR_ARG): B out of range, sb NULL, every field NULL (nmpc_batch_set_stage_limits: every array
  * NULL), n < 0, a NULL handle. */
 typedef struct nmpc_stage_bounds {
@@ -488,6 +488,42 @@ int nmpc_batch_stage_bounds(nmpc_batch* b, void** table, size_t* bytes);
 /* Turn the stage table off: launches use the per-robot table's or the handle's one box again. The next writer call
  * starts a fresh table. (Host-side switch: it applies to the launches enqueued after it.) */
 int nmpc_batch_clear_stage_bounds(nmpc_batch* b);
+
+/* Per-robot model parameters. A fleet of one model family mixes vehicles: two wheelbases of the same differential
+ * base, loaded and empty trucks whose tau_v differ by a factor of two or three (the reference runs one node per robot,
+ * each sending its own geometry and time constants through {name}_acados_update_params, NMPCNavControlDiff.cpp:44-46,
+ * NMPCNavControlROS.cpp:96-110,164-176,234-259). The handle therefore owns a third device table, the model table:
+ * [NP][capacity], fp32, instance-minor, row j = every robot's p[j] (diff {b, tau_v}, omni4 {l1 + l2, tau_v}, tric
+ * {d, tau_v, tau_a}); 8 or 12 bytes per robot. It is allocated by the first nmpc_batch_set_robot_model call and starts
+ * with the handle's own p in every column (the fp32 values the kernels take from nmpc_model_params).
+ * Rules:
+ *   - While the table is on, every launch of the handle -- nmpc_batch_solve, _solve_iterate, _run, _run_path,
+ *     _follow_path and both node ticks -- takes robot i's p from column i wherever it read the handle's p: the RK4
+ *     linearisation and its sensitivities, the constant rows of the stage Jacobian, run mode's direct kinematics of
+ *     the measured velocity, and the inverse kinematics of the command. nmpc_batch_set_params' p then reaches no
+ *     launch (it is what a table allocated or cleared later starts from). dt, dt_ctrl, the QP options, terminal_hack
+ *     and tric_sin_bug stay with the handle.
+ *   - While it is off (never written, or after nmpc_batch_clear_robot_model) every launch computes exactly what it
+ *     computed without this interface.
+ *   - The three tables are independent: any combination of them being on or off is legal.
+ *   - The writer is one small launch on `stream`, with no host synchronisation and no host-side validation. Warm
+ *     flags are left alone when a column changes.
+ *   - A NaN or a zero in a parameter fails that robot alone with status 1, through the NaN its dynamics then
+ *     produce; no other robot changes. The robot keeps its iterate and carried refs and gets a stop command, as after
+ *     any failed solve.
+ *   - The harness plant (nmpc_fleet_sim_step, _step_renew) reads the robot's column too while the table is on, in
+ *     its RK4 step and in the velocity it measures, so the closed loop simulates the vehicle the controller models.
+ *   - Out of scope: per-robot dt and QP options, parameters that vary along the horizon, and the capsule ABI, which
+ *     keeps one p per capsule and keeps rejecting stage-varying parameters.
+ * Argument errors (NMPC_ERR_ARG): B out of range, p NULL, a NULL handle. */
+/* Write the columns of robots [0, B) where mask[i] != 0 (mask [B] device, NULL: all) from p [NP][B] (device). */
+int nmpc_batch_set_robot_model(nmpc_batch* b, int B, const float* p, const unsigned char* mask, void* stream);
+/* The table's device view for checkpoints: *table [rows][stride] (rows = NP, stride = capacity), or NULL while the
+ * table is off. Each output may be NULL. */
+int nmpc_batch_robot_model(nmpc_batch* b, float** table, int* rows, int* stride);
+/* Turn the model table off: launches use the handle's p again. The next writer call starts a fresh table from the
+ * handle's p. (Host-side switch: it applies to the launches enqueued after it.) */
+int nmpc_batch_clear_robot_model(nmpc_batch* b);
 
 /* Record layout of the team kernel's single-direction scratch records, a per-handle choice fixed at create time
  * and changed only by this call (never by other handles):

@@ -121,6 +121,7 @@ BATCH_SYMBOLS = [
     "nmpc_batch_clear_robot_params",
     "nmpc_batch_set_stage_bounds", "nmpc_batch_set_stage_limits", "nmpc_batch_shift_stage_bounds",
     "nmpc_batch_stage_bounds", "nmpc_batch_clear_stage_bounds",
+    "nmpc_batch_set_robot_model", "nmpc_batch_robot_model", "nmpc_batch_clear_robot_model",
     "nmpc_fleet_sim_step", "nmpc_fleet_sim_step_renew", "nmpc_fleet_hash",
     "nmpc_last_error", "nmpc_version", "nmpc_path_discretize", "nmpc_path_nearest", "nmpc_codegen_default", "nmpc_capsule_new",
     "nmpc_capsule_delete", "nmpc_capsule_create", "nmpc_capsule_reset", "nmpc_capsule_update_params",
@@ -198,6 +199,9 @@ def lib():
     L.nmpc_batch_shift_stage_bounds.argtypes = [vp, i, i, vp, vp]
     L.nmpc_batch_stage_bounds.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
     L.nmpc_batch_clear_stage_bounds.argtypes = [vp]
+    L.nmpc_batch_set_robot_model.argtypes = [vp, i, vp, vp, vp]
+    L.nmpc_batch_robot_model.argtypes = [vp, ctypes.POINTER(vp), c_int_p, c_int_p]
+    L.nmpc_batch_clear_robot_model.argtypes = [vp]
     L.nmpc_fleet_sim_step.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     L.nmpc_fleet_sim_step_renew.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(FleetRenew), vp]
     L.nmpc_fleet_hash.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint]

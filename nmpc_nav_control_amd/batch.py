@@ -86,6 +86,7 @@ class BatchSolver:
         self.params.N = self.N
         d = model_dims(model)
         self.nx, self.nu, self.ny, self.nbx, self.nbu = d["nx"], d["nu"], d["ny"], d["nbx"], d["nbu"]
+        self.np = d["np"]
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             check(lib().nmpc_batch_create(ctypes.byref(self.params), self.capacity, ctypes.byref(self._h)),
@@ -272,10 +273,31 @@ class BatchSolver:
         """Turn the stage table off: launches use one box per robot again."""
         check(lib().nmpc_batch_clear_stage_bounds(self._h), "nmpc_batch_clear_stage_bounds")
 
+    def set_robot_model(self, p, mask=None, stream=None):
+        """Per-robot model parameters (nmpc_batch_set_robot_model): p a float32 device tensor [np][B] (diff {b, tau_v},
+        omni4 {l1 + l2, tau_v}, tric {d, tau_v, tau_a}); mask uint8 [B] selects the robots (None: all). One launch on
+        the stream; from then on every launch of this solver, and the harness plant, takes each robot's p from the
+        model table (until clear_robot_model)."""
+        B = self._batch_of(p)
+        check(lib().nmpc_batch_set_robot_model(self._h, B, _ptr(p, F32, (self.np, B), "p"),
+                                               _ptr(mask, U8, (B,), "mask"), _stream(stream)),
+              "nmpc_batch_set_robot_model")
+
+    def robot_model(self):
+        """View of the model table [np][cap], or None while it is off (nmpc_batch_robot_model)."""
+        tb, rows, stride = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        check(lib().nmpc_batch_robot_model(self._h, ctypes.byref(tb), ctypes.byref(rows), ctypes.byref(stride)),
+              "nmpc_batch_robot_model")
+        return _DeviceView(tb.value, (rows.value, stride.value), self.device) if tb.value else None
+
+    def clear_robot_model(self):
+        """Turn the model table off: launches use the handle's p again."""
+        check(lib().nmpc_batch_clear_robot_model(self._h), "nmpc_batch_clear_robot_model")
+
     def save_state(self):
         """Device copies of everything a solve reads from the handle: iterate, carried refs, warm start (five
         tensors), then the per-robot table as a tensor when it is on, then the stage table as
-        {"stage_bounds": bytes} when it is on."""
+        {"stage_bounds": bytes} and the model table as {"robot_model": tensor} when they are on."""
         saved = [v.to_tensor() for v in self.state() + self.warm_state()]
         rp = self.robot_params()
         if rp is not None:
@@ -283,13 +305,23 @@ class BatchSolver:
         sb = self.stage_bounds()
         if sb is not None:
             saved.append({"stage_bounds": sb.to_tensor()})
+        rm = self.robot_model()
+        if rm is not None:
+            saved.append({"robot_model": rm.to_tensor()})
         return saved
 
     def restore_state(self, saved):
         for v, t in zip(self.state() + self.warm_state(), saved):
             v.copy_from(t)
-        stage = [e["stage_bounds"] for e in saved[5:] if isinstance(e, dict)]
+        stage = [e["stage_bounds"] for e in saved[5:] if isinstance(e, dict) and "stage_bounds" in e]
+        model = [e["robot_model"] for e in saved[5:] if isinstance(e, dict) and "robot_model" in e]
         saved = [e for e in saved if not isinstance(e, dict)]
+        if model:
+            # the table's columns, written through the writer (which allocates and switches the table on)
+            self.set_robot_model(model[0].to(self.device).contiguous())
+            torch.cuda.synchronize()
+        else:
+            self.clear_robot_model()
         if stage:
             # (a shift by no stage allocates the table and switches it on; the bytes then replace its first fill)
             self.shift_stage_bounds(0)

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kFleetBlock) void k_fleet_sim(KParams P, int B, int
                                                           float* pose, float* vel, float* steer, const float* u0,
                                                           const int* status, const float* carried, float* traj,
                                                           int* traj_len, int advance, nmpc_fleet_renew R,
-                                                          nmpc_fleet_stats S)
+                                                          nmpc_fleet_stats S, const float* rmodel)
 {
     constexpr int NX = M::NX, NU = M::NU;
     constexpr int RPB = kFleetBlock / kFleetLanes;  // robots per block
@@ -96,6 +96,10 @@ __global__ __launch_bounds__(kFleetBlock) void k_fleet_sim(KParams P, int B, int
         float ps[3] = {pose[i], pose[Bn + i], pose[2 * Bn + i]};
         float v3[3] = {vel[i], vel[Bn + i], vel[2 * Bn + i]};
         const float st0 = steer ? steer[i] : 0.0f;
+        // the plant's model parameters: the robot's column of the handle's model table when it is on, so that the
+        // closed loop simulates the vehicle its controller models; else the handle's
+        const ModelVals mvals = model_vals<M>(P, rmodel, (size_t)stride, i);
+        const ModelPar mp = model_par(P, mvals);
         float u[NU], cr[M::NBX], pp[6];
 #pragma unroll
         for (int j = 0; j < NU; j++) u[j] = advance ? u0[(size_t)j * Bn + i] : 0.0f;
@@ -125,23 +129,23 @@ __global__ __launch_bounds__(kFleetBlock) void k_fleet_sim(KParams P, int B, int
             x[0] = ps[0];
             x[1] = ps[1];
             x[2] = ps[2];
-            M::direct_kin(v3, st0, P, x + 3);
+            M::direct_kin(v3, st0, mp, x + 3);
             // ref states at the solve's x0 = carried (already advanced by the post-solve) - u0 * dt_ctrl
 #pragma unroll
             for (int j = 0; j < M::NBX; j++) x[M::idxbx(j)] = cr[j] - u[j] * P.dt_ctrl;
-            rk4<M>(x, u, P, P.dt_ctrl, xn);
+            rk4<M>(x, u, mp, P.dt_ctrl, xn);
             ps[0] = xn[0];
             ps[1] = xn[1];
             ps[2] = xn[2];
             float nv[3];
-            if (M::ID == kDiff) {
+            if constexpr (M::ID == kDiff) {
                 nv[0] = 0.5f * (xn[3] + xn[4]);
                 nv[1] = 0.0f;
-                nv[2] = (xn[4] - xn[3]) / P.p[0];
-            } else if (M::ID == kOmni4) {
+                nv[2] = (xn[4] - xn[3]) / mp.p[0];
+            } else if constexpr (M::ID == kOmni4) {
                 nv[0] = 0.25f * (xn[3] - xn[4] + xn[5] - xn[6]);
                 nv[1] = 0.25f * (-xn[3] - xn[4] + xn[5] + xn[6]);
-                nv[2] = -(xn[3] + xn[4] + xn[5] + xn[6]) / (2.0f * P.p[0]);
+                nv[2] = -(xn[3] + xn[4] + xn[5] + xn[6]) / (2.0f * mp.p[0]);
             } else {
                 nv[0] = xn[3];
                 nv[1] = 0.0f;
@@ -252,7 +256,8 @@ __global__ __launch_bounds__(kFleetBlock) void k_fleet_sim(KParams P, int B, int
 template <class M>
 hipError_t launch_fleet_sim(const KParams& P, int B, int stride, float* path, float* s, float* pose, float* vel,
                             float* steer, const float* u0, const int* status, const float* carried, float* traj,
-                            int* traj_len, int advance, const nmpc_fleet_renew* renew, hipStream_t stream)
+                            int* traj_len, int advance, const nmpc_fleet_renew* renew, const float* rmodel,
+                            hipStream_t stream)
 {
     if (B <= 0) return hipSuccess;
     constexpr int rpb = kFleetBlock / kFleetLanes;
@@ -262,14 +267,14 @@ hipError_t launch_fleet_sim(const KParams& P, int B, int stride, float* path, fl
     if (renew && renew->stats) S = *renew->stats;
     R.stats = nullptr;  // host memory: the kernel gets S by value
     hipLaunchKernelGGL(k_fleet_sim<M>, dim3((B + rpb - 1) / rpb), dim3(kFleetBlock), 0, stream, P, B, stride, path, s,
-                       pose, vel, steer, u0, status, carried, traj, traj_len, advance, R, S);
+                       pose, vel, steer, u0, status, carried, traj, traj_len, advance, R, S, rmodel);
     return hipGetLastError();
 }
 
 #define INST(M)                                                                                                      \
     template hipError_t launch_fleet_sim<M>(const KParams&, int, int, float*, float*, float*, float*, float*,       \
                                             const float*, const int*, const float*, float*, int*, int,              \
-                                            const nmpc_fleet_renew*, hipStream_t);
+                                            const nmpc_fleet_renew*, const float*, hipStream_t);
 INST(Diff2)
 INST(Omni4)
 INST(Tric3)

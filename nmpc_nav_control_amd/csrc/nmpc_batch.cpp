@@ -68,6 +68,11 @@ struct nmpc_batch {
     // nmpc_kernels.hpp), allocated by the first writer; sb_on: launches read it (resident_args)
     float* sbounds = nullptr;
     bool sb_on = false;
+    // per-robot model parameters (nmpc_batch_set_robot_model): the model table [np][capacity], allocated by the first
+    // writer; rm_on: launches and the harness plant read it (resident_args, fleet_sim)
+    float* rmodel = nullptr;
+    int np = 0;
+    bool rm_on = false;
 };
 
 namespace {
@@ -332,6 +337,7 @@ KArgs resident_args(const nmpc_batch* b, int B)
     a.scratch = b->scratch;
     if (b->rp_on) a.rparams = b->rparams;
     if (b->sb_on) a.sbounds = b->sbounds;
+    if (b->rm_on) a.rmodel = b->rmodel;
     return a;
 }
 
@@ -354,6 +360,22 @@ int rp_table(nmpc_batch* b, hipStream_t s)
     for (int i = 0; i < b->nx; i++) col.v[b->rp.off[kRpWe] + i] = k.We[i];
     const int rc = hip_err(launch_rp_fill(b->rparams, b->capacity, rows, col, s), "robot_params fill launch");
     if (rc == NMPC_OK) b->rp_on = true;
+    return rc;
+}
+
+// The model table ready for a writer on stream s: allocated at the first call, and when it was off filled with the
+// handle's own p (KParams' fp32 values)
+int rm_table(nmpc_batch* b, hipStream_t s)
+{
+    if (b->rm_on) return NMPC_OK;
+    if (!b->rmodel) {
+        const hipError_t e = hipMalloc(&b->rmodel, sizeof(float) * (size_t)b->np * (size_t)b->capacity);
+        if (e != hipSuccess) return hip_err(e, "hipMalloc");
+    }
+    RmColumn col{};
+    for (int i = 0; i < b->np; i++) col.v[i] = b->kp.p[i];
+    const int rc = hip_err(launch_rm_fill(b->rmodel, b->capacity, b->np, col, s), "robot_model fill launch");
+    if (rc == NMPC_OK) b->rm_on = true;
     return rc;
 }
 
@@ -548,8 +570,7 @@ int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** o
     nmpc_batch* b = new nmpc_batch();
     b->prm = *prm;
     b->capacity = capacity;
-    int np;
-    dims_of(prm->model, &b->nx, &b->nu, &b->nbx, &b->nbu, &np);
+    dims_of(prm->model, &b->nx, &b->nu, &b->nbx, &b->nbu, &b->np);
     b->ny = b->nx + b->nu;
     b->kp = to_kparams(*prm, b->nx, b->nu, b->nbx, b->nbu);
     b->rp = rp_rows(b->nx, b->nu, b->nbx, b->nbu);
@@ -619,6 +640,7 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->node_status);
     (void)hipFree(b->rparams);
     (void)hipFree(b->sbounds);
+    (void)hipFree(b->rmodel);
     delete b;
     return NMPC_OK;
 }
@@ -1078,6 +1100,34 @@ int nmpc_batch_clear_stage_bounds(nmpc_batch* b)
     return NMPC_OK;
 }
 
+int nmpc_batch_set_robot_model(nmpc_batch* b, int B, const float* p, const unsigned char* mask, void* stream)
+{
+    // the checks that need no handle come first
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!p) return set_err(NMPC_ERR_ARG, "robot model: p is NULL");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (B == 0) return NMPC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = rm_table(b, s)) return rc;
+    return hip_err(launch_rm_set(b->rmodel, b->capacity, B, b->np, p, mask, s), "robot_model launch");
+}
+
+int nmpc_batch_robot_model(nmpc_batch* b, float** table, int* rows, int* stride)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (table) *table = b->rm_on ? b->rmodel : nullptr;
+    if (rows) *rows = b->np;
+    if (stride) *stride = b->capacity;
+    return NMPC_OK;
+}
+
+int nmpc_batch_clear_robot_model(nmpc_batch* b)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    b->rm_on = false;  // (the allocation stays for the next writer, which refills it)
+    return NMPC_OK;
+}
+
 int nmpc_batch_set_record_layout(nmpc_batch* b, int layout)
 {
     if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
@@ -1146,7 +1196,8 @@ int fleet_sim(nmpc_batch* b, int B, float* path, float* s, float* pose, float* v
     if (!path || !s || !pose || !vel || !traj || (advance && !u0)) return set_err(NMPC_ERR_ARG, "NULL argument");
     const hipError_t e = with_model(b->prm.model, [&](auto m) {
         return launch_fleet_sim<decltype(m)>(b->kp, B, b->capacity, path, s, pose, vel, steer, u0, status, b->carried,
-                                             traj, traj_len, advance, renew, (hipStream_t)stream);
+                                             traj, traj_len, advance, renew, b->rm_on ? b->rmodel : nullptr,
+                                             (hipStream_t)stream);
     });
     return hip_err(e, "fleet_sim launch");
 }

@@ -101,6 +101,9 @@ struct KArgs {
     // horizon (sb_at below); nullptr: the table is off and a robot's box is the same at every stage (rparams, else
     // KParams). While it is on, the bound rows of rparams and of KParams reach no launch
     const float* sbounds;
+    // per-robot model parameters (robot_model.hip): the handle's model table [NP][sstride]; nullptr: the table is off
+    // and every robot takes KParams::p. While it is on, KParams::p reaches no launch (robot_vals, sqp_steps.hpp)
+    const float* rmodel;
 };
 
 // Rows of the per-robot table, in this order: lbx[NBX] ubx[NBX] lbu[NBU] ubu[NBU] W[NY] W_e[NX]
@@ -149,10 +152,12 @@ hipError_t launch_sqp_rti_rowpar(const KParams& P, const KArgs& a, int mode, hip
 template <class M>
 size_t rowpar_lds_bytes(int N, int mode, int seg);
 constexpr int kSegMax = 16;  // most horizon segments of the segmented row-parallel kernel
+// rmodel: the handle's model table when it is on (the plant then steps each robot with its own column), else nullptr
 template <class M>
 hipError_t launch_fleet_sim(const KParams& P, int B, int stride, float* path, float* s, float* pose, float* vel,
                             float* steer, const float* u0, const int* status, const float* carried, float* traj,
-                            int* traj_len, int advance, const nmpc_fleet_renew* renew, hipStream_t stream);
+                            int* traj_len, int advance, const nmpc_fleet_renew* renew, const float* rmodel,
+                            hipStream_t stream);
 hipError_t launch_team_order(const int* key, int B, int layout, int* sorted, int* order, hipStream_t stream);
 // node ticks: the robots with active[i] != 0 first (hardest first by key when `sorted`, else in index order), the
 // others behind them; n_active[0] = their count
@@ -172,6 +177,14 @@ hipError_t launch_rp_set(float* table, int cap, int B, const RpRows& rr, const n
 hipError_t launch_rp_limits(float* table, int cap, int B, const RpRows& rr, int tric, const float* v_max,
                             const float* a_max, const float* alpha_min, const float* alpha_max,
                             const float* dalpha_max, const unsigned char* mask, hipStream_t stream);
+// the model table's writers (robot_model.hip), each one launch: every robot's column = p (the first `cap` robots); and
+// the np rows of src ([np][B]) for the robots with mask[i] != 0 (nullptr: all)
+struct RmColumn {
+    float v[3];
+};
+hipError_t launch_rm_fill(float* table, int cap, int np, const RmColumn& p, hipStream_t stream);
+hipError_t launch_rm_set(float* table, int cap, int B, int np, const float* src, const unsigned char* mask,
+                         hipStream_t stream);
 // the stage table's writers (stage_bounds.hip), each one launch. sb: the table, N + 1 stages of `cap` robots.
 // fill: every stage of every robot = the robot's column of the per-robot table rp (rows rr, stride cap) when rp is
 // not nullptr, else col's first sb_rows values (lbx ubx lbu ubu of the handle). set: the non-NULL fields of s for the

@@ -14,15 +14,18 @@
 namespace nmpc {
 
 // Uniform (per-launch) parameters: model parameters, bounds, stage weights, QP options.
-// INVARIANT the team kernel relies on: dt and the model parameters p are the same for every robot of a launch, so the
-// state-independent rows of [B A] (rows >= NGV of each model, Model::gmask) are bit-identical for every robot; the
+// The model parameters p reach the model functors as the model's Par value (below), one per robot: built from p here
+// when the handle's model table is off (KArgs::rmodel == nullptr), from the robot's column of that table when it is on.
+// INVARIANT the team kernel's table-off launches rely on: dt and p are then the same for every robot of a launch, so
+// the state-independent rows of [B A] (rows >= NGV of each model, Model::gmask) are bit-identical for every robot; the
 // column-form M block (gconst_load, team_common.hpp) reads them from each wave's first team and applies them to all
-// four. Per-robot model parameters would break this and need the row form (-DNMPC_MROW) or per-team constants;
-// tests/test_gpu_split.py::test_constant_rows_per_launch checks the column form against that build.
+// four; tests/test_gpu_split.py::test_constant_rows_per_launch checks that form against the row-form build. It does
+// not hold with the model table on: those launches run instantiations of their own whose M block broadcasts the
+// constant entries from the team's own lanes (m_block_team, team_common.hpp; tests/test_gpu_robot_model.py).
 struct KParams {
     int N;
     float dt, dt_ctrl;
-    float p[3];
+    float p[3];  // the handle's model parameters (the source of Par while the model table is off)
     float lbx[4], ubx[4], lbu[4], ubu[4];
     float W[15];   // stage weight diagonal [Q; R]
     float We[11];  // terminal weight diagonal (constructor value; diff run() may scale the pose part)
@@ -43,6 +46,22 @@ struct KParams {
 };
 
 enum ModelId { kDiff = 0, kOmni4 = 1, kTric = 2 };
+
+// One robot's model parameters as the model functors take them: p (diff {b, tau_v}, omni4 {l1 + l2, tau_v}, tric
+// {d, tau_v, tau_a}) and tric's sin_bug switch, which stays the handle's. A view, not a copy: with the model table off
+// p points at KParams::p, so a functor's read is the kernel-argument read it always was and the table-off kernels keep
+// their code; with the table on it points at the robot's values, loaded once in the prologue (ModelVals below).
+// The functors form the reciprocals where they use them, as they did on KParams::p, and the compiler hoists them out
+// of P0's loop. Computed once by hand in the prologue instead, the table-off team kernel was no longer the parent's
+// code and lost 0.9 % on the metric config (profiles/r07/ab/robot_model.txt).
+struct ModelPar {
+    const float* p;
+    const int* sin_bug;
+};
+// the robot's column of the model table, held in registers
+struct ModelVals {
+    float v[3];
+};
 
 // Column bitmask of one row of the discrete Jacobian [B A] in the team lane order (bit v: input v for v < NU,
 // state v - NU above), from a pattern string ('1' = structurally nonzero). gmask(i) of a model gives its constant
@@ -72,10 +91,11 @@ struct Diff2 {
     }
     __host__ __device__ static constexpr int idxbx(int i) { return 5 + i; }
     __host__ __device__ static constexpr int idxbu(int i) { return i; }
+    using Par = ModelPar;
 
-    __device__ static inline void f(const float* x, const float* u, const KParams& P, float* xd)
+    __device__ static inline void f(const float* x, const float* u, const Par& mp, float* xd)
     {
-        const float ib = 1.0f / P.p[0], it = 1.0f / P.p[1];
+        const float ib = 1.0f / mp.p[0], it = 1.0f / mp.p[1];
         float s, c;
         __sincosf(x[2], &s, &c);
         const float v = 0.5f * (x[4] + x[3]);
@@ -89,9 +109,9 @@ struct Diff2 {
     }
     // dK[r][j] = sum_l Jx[r][l] S[l][j] + Ju[r][j - NX]   (NV = NX + NU columns)
     template <int NV>
-    __device__ static inline void jvp(const float* x, const float (&S)[NX][NV], const KParams& P, float (&dK)[NX][NV])
+    __device__ static inline void jvp(const float* x, const float (&S)[NX][NV], const Par& mp, float (&dK)[NX][NV])
     {
-        const float ib = 1.0f / P.p[0], it = 1.0f / P.p[1];
+        const float ib = 1.0f / mp.p[0], it = 1.0f / mp.p[1];
         float s, c;
         __sincosf(x[2], &s, &c);
         const float v = 0.5f * (x[4] + x[3]);
@@ -108,16 +128,16 @@ struct Diff2 {
         }
     }
     // NMPCNavControlDiff.cpp:183-187 (vel = {v, vn, w})
-    __device__ static inline void direct_kin(const float* vel, float, const KParams& P, float* xv)
+    __device__ static inline void direct_kin(const float* vel, float, const Par& mp, float* xv)
     {
-        xv[0] = vel[0] - 0.5f * P.p[0] * vel[2];
-        xv[1] = vel[0] + 0.5f * P.p[0] * vel[2];
+        xv[0] = vel[0] - 0.5f * mp.p[0] * vel[2];
+        xv[1] = vel[0] + 0.5f * mp.p[0] * vel[2];
     }
     // NMPCNavControlDiff.cpp:189-193 -> cmd {v, w, 0}
-    __device__ static inline void inverse_kin(const float* r, const KParams& P, float* cmd)
+    __device__ static inline void inverse_kin(const float* r, const Par& mp, float* cmd)
     {
         cmd[0] = 0.5f * (r[1] + r[0]);
-        cmd[1] = (r[1] - r[0]) / P.p[0];
+        cmd[1] = (r[1] - r[0]) / mp.p[0];
         cmd[2] = 0.0f;
     }
 };
@@ -138,10 +158,11 @@ struct Omni4 {
     }
     __host__ __device__ static constexpr int idxbx(int i) { return 7 + i; }
     __host__ __device__ static constexpr int idxbu(int i) { return i; }
+    using Par = ModelPar;
 
-    __device__ static inline void f(const float* x, const float* u, const KParams& P, float* xd)
+    __device__ static inline void f(const float* x, const float* u, const Par& mp, float* xd)
     {
-        const float it = 1.0f / P.p[1], iw = 1.0f / (2.0f * P.p[0]);
+        const float it = 1.0f / mp.p[1], iw = 1.0f / (2.0f * mp.p[0]);
         float s, c;
         __sincosf(x[2], &s, &c);
         const float v = 0.25f * (x[3] - x[4] + x[5] - x[6]);
@@ -155,9 +176,9 @@ struct Omni4 {
         for (int i = 0; i < 4; i++) xd[7 + i] = u[i];
     }
     template <int NV>
-    __device__ static inline void jvp(const float* x, const float (&S)[NX][NV], const KParams& P, float (&dK)[NX][NV])
+    __device__ static inline void jvp(const float* x, const float (&S)[NX][NV], const Par& mp, float (&dK)[NX][NV])
     {
-        const float it = 1.0f / P.p[1], iw = 1.0f / (2.0f * P.p[0]);
+        const float it = 1.0f / mp.p[1], iw = 1.0f / (2.0f * mp.p[0]);
         float s, c;
         __sincosf(x[2], &s, &c);
         const float v = 0.25f * (x[3] - x[4] + x[5] - x[6]);
@@ -177,20 +198,20 @@ struct Omni4 {
         }
     }
     // NMPCNavControlOmni4.cpp:185-192
-    __device__ static inline void direct_kin(const float* vel, float, const KParams& P, float* xv)
+    __device__ static inline void direct_kin(const float* vel, float, const Par& mp, float* xv)
     {
-        const float hl = 0.5f * P.p[0] * vel[2];
+        const float hl = 0.5f * mp.p[0] * vel[2];
         xv[0] = vel[0] - vel[1] - hl;
         xv[1] = -vel[0] - vel[1] - hl;
         xv[2] = vel[0] + vel[1] - hl;
         xv[3] = -vel[0] + vel[1] - hl;
     }
     // NMPCNavControlOmni4.cpp:194-200 -> cmd {v, vn, w}
-    __device__ static inline void inverse_kin(const float* r, const KParams& P, float* cmd)
+    __device__ static inline void inverse_kin(const float* r, const Par& mp, float* cmd)
     {
         cmd[0] = 0.25f * (r[0] - r[1] + r[2] - r[3]);
         cmd[1] = 0.25f * (-r[0] - r[1] + r[2] + r[3]);
-        cmd[2] = -(r[0] + r[1] + r[2] + r[3]) / (2.0f * P.p[0]);
+        cmd[2] = -(r[0] + r[1] + r[2] + r[3]) / (2.0f * mp.p[0]);
     }
 };
 
@@ -207,14 +228,15 @@ struct Tric3 {
     }
     __host__ __device__ static constexpr int idxbx(int i) { return 5 + i; }
     __host__ __device__ static constexpr int idxbu(int i) { return i; }
+    using Par = ModelPar;
 
-    __device__ static inline void f(const float* x, const float* u, const KParams& P, float* xd)
+    __device__ static inline void f(const float* x, const float* u, const Par& mp, float* xd)
     {
-        const float id = 1.0f / P.p[0], itv = 1.0f / P.p[1], ita = 1.0f / P.p[2];
+        const float id = 1.0f / mp.p[0], itv = 1.0f / mp.p[1], ita = 1.0f / mp.p[2];
         float s, c, sa, ca;
         __sincosf(x[2], &s, &c);
         __sincosf(x[4], &sa, &ca);
-        const float cal = P.sin_bug ? sa : ca;  // tric_amr_model.py:45
+        const float cal = *mp.sin_bug ? sa : ca;  // tric_amr_model.py:45
         xd[0] = x[3] * c * cal;
         xd[1] = x[3] * s * cal;
         xd[2] = x[3] * id * sa;
@@ -224,14 +246,14 @@ struct Tric3 {
         xd[6] = u[1];
     }
     template <int NV>
-    __device__ static inline void jvp(const float* x, const float (&S)[NX][NV], const KParams& P, float (&dK)[NX][NV])
+    __device__ static inline void jvp(const float* x, const float (&S)[NX][NV], const Par& mp, float (&dK)[NX][NV])
     {
-        const float id = 1.0f / P.p[0], itv = 1.0f / P.p[1], ita = 1.0f / P.p[2];
+        const float id = 1.0f / mp.p[0], itv = 1.0f / mp.p[1], ita = 1.0f / mp.p[2];
         float s, c, sa, ca;
         __sincosf(x[2], &s, &c);
         __sincosf(x[4], &sa, &ca);
-        const float cal = P.sin_bug ? sa : ca;
-        const float dcal = P.sin_bug ? ca : -sa;
+        const float cal = *mp.sin_bug ? sa : ca;
+        const float dcal = *mp.sin_bug ? ca : -sa;
         const float v = x[3];
 #pragma unroll
         for (int j = 0; j < NV; j++) {
@@ -246,13 +268,13 @@ struct Tric3 {
         }
     }
     // NMPCNavControlTric.cpp:97-98: x0[v] = measured v, x0[alpha] = steering wheel angle
-    __device__ static inline void direct_kin(const float* vel, float steer, const KParams&, float* xv)
+    __device__ static inline void direct_kin(const float* vel, float steer, const Par&, float* xv)
     {
         xv[0] = vel[0];
         xv[1] = steer;
     }
     // NMPCNavControlTric.cpp:161-162 -> cmd {v, alpha, 0}
-    __device__ static inline void inverse_kin(const float* r, const KParams&, float* cmd)
+    __device__ static inline void inverse_kin(const float* r, const Par&, float* cmd)
     {
         cmd[0] = r[0];
         cmd[1] = r[1];
@@ -260,11 +282,30 @@ struct Tric3 {
     }
 };
 
+// A robot's Par on the launch's own parameters (model table off) ...
+__device__ inline ModelPar model_par(const KParams& P) { return ModelPar{P.p, &P.sin_bug}; }
+// ... or on the values v of its column (model_vals)
+__device__ inline ModelPar model_par(const KParams& P, const ModelVals& v) { return ModelPar{v.v, &P.sin_bug}; }
+// column `inst` of the model table t, [NP][cap] (every lane of a robot loads the same NP floats); t == nullptr: the
+// launch's own p
+template <class M>
+__device__ inline ModelVals model_vals(const KParams& P, const float* t, size_t cap, int inst)
+{
+    ModelVals o;
+#pragma unroll
+    for (int j = 0; j < 3; j++) o.v[j] = P.p[j];
+    if (t) {
+#pragma unroll
+        for (int j = 0; j < M::NP; j++) o.v[j] = t[(size_t)j * cap + inst];
+    }
+    return o;
+}
+
 // One RK4 step with forward sensitivities (acados ERK default: 4 stages, 1 step, forward VDE):
 // xn = phi(x, u); A = d phi / dx; B = d phi / du.
 template <class M>
-__device__ inline void rk4_sens(const float* x, const float* u, const KParams& P, float* xn, float (&A)[M::NX][M::NX],
-                                float (&Bm)[M::NX][M::NU])
+__device__ inline void rk4_sens(const float* x, const float* u, const KParams& P, const ModelPar& mp, float* xn,
+                                float (&A)[M::NX][M::NX], float (&Bm)[M::NX][M::NU])
 {
     constexpr int NX = M::NX, NU = M::NU, NV = NX + NU;
     const float h = P.dt;
@@ -280,8 +321,8 @@ __device__ inline void rk4_sens(const float* x, const float* u, const KParams& P
     const float wgt[4] = {1.0f, 2.0f, 2.0f, 1.0f};
 #pragma unroll
     for (int st = 0; st < 4; st++) {
-        M::f(xs, u, P, k);
-        M::template jvp<NV>(xs, S, P, dK);
+        M::f(xs, u, mp, k);
+        M::template jvp<NV>(xs, S, mp, dK);
 #pragma unroll
         for (int i = 0; i < NX; i++) {
             acc[i] = (st == 0) ? k[i] : acc[i] + wgt[st] * k[i];
@@ -311,7 +352,7 @@ __device__ inline void rk4_sens(const float* x, const float* u, const KParams& P
 
 // RK4 without sensitivities (plant simulation of the bench harness).
 template <class M>
-__device__ inline void rk4(const float* x, const float* u, const KParams& P, float h, float* xn)
+__device__ inline void rk4(const float* x, const float* u, const typename M::Par& mp, float h, float* xn)
 {
     constexpr int NX = M::NX;
     float k[NX], xs[NX], acc[NX];
@@ -321,7 +362,7 @@ __device__ inline void rk4(const float* x, const float* u, const KParams& P, flo
     const float wgt[4] = {1.0f, 2.0f, 2.0f, 1.0f};
 #pragma unroll
     for (int st = 0; st < 4; st++) {
-        M::f(xs, u, P, k);
+        M::f(xs, u, mp, k);
 #pragma unroll
         for (int i = 0; i < NX; i++) acc[i] = (st == 0) ? k[i] : acc[i] + wgt[st] * k[i];
         if (st < 3) {

@@ -102,8 +102,16 @@ __device__ __attribute__((aligned(16))) float g_rec_sentinel[8] = {kFar, kFar, 0
 // RP: the launch reads the handle's per-robot table of bounds and weights or its stage table (KArgs::rparams or
 // KArgs::sbounds != nullptr; the launcher picks it from the pointers). P0 then loads each lane's box per stage
 // (stage_box). Launches with both tables off run the RP = false instantiations, which mention neither table
+// MT: the launch reads the handle's model table (KArgs::rmodel != nullptr). Each team loads its robot's parameters in
+// the prologue (robot_vals), and the column-form M block takes its constant rows from the team's own lanes
+// (m_block_team: the same structural-nonzero FMAs with broadcast operands): m_block's come from the wave's first team
+// and are right only while the four robots of a wave share their model parameters. The row form (mrow_pg_block) was
+// measured against it and lost 2.6 to 8.6 % (profiles/r07/ab/robot_model.txt). MT implies RP: these instantiations
+// serve every combination of the other two tables (stage_box_ctx's fallback), so the model table adds one
+// instantiation per launch shape, not two. Launches with all three tables off run the RP = MT = false
+// instantiations, which mention none of them
 constexpr int kModeRunPath = 2;
-template <class M, bool MS, bool SD, int MODE, bool SP, bool RP>
+template <class M, bool MS, bool SD, int MODE, bool SP, bool RP, bool MT>
 __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 {
     constexpr int mode = MODE == kModeRunPath ? kModeRun : MODE;
@@ -131,7 +139,11 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     const float sc = P.dt, w_lane = lc.w_lane, h_stage = lc.h_stage, lo_b = lc.lo_b, hi_b = lc.hi_b;
     // RP: where P0 loads this lane's box of a stage from (the stage table, else the per-robot table's one box)
     StageBox sbx{};
-    if constexpr (RP) sbx = stage_box_ctx<M>(a, inst, lc, r);
+    if constexpr (RP) sbx = stage_box_ctx<M, MT>(a, inst, lc, r);
+    // the robot's model parameters: the handle's (a view of KParams::p), or (MT) its column of the model table
+    ModelVals mvals{};
+    if constexpr (MT) mvals = robot_vals<M>(P, a, inst);
+    const ModelPar mp = MT ? model_par(P, mvals) : model_par(P);
     // this lane's record of stage k: tbase + k * KS
     // idle slots (r >= NV) alias slot 0's record: their (unpredicated) loads then read valid data and touch no
     // extra cache lines; they never store
@@ -210,7 +222,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
 
     // ---- x0 (every lane keeps the full vector) ----------------------------------------------------------
     float x0[NX];
-    const X0Lane xl = load_x0<M, RP>(P, a, mode, inst, lc, x0);
+    const X0Lane xl = load_x0<M, RP>(P, a, mode, inst, lc, mp, x0);
     const float pose_th = xl.pose_th, x0_lane = xl.x0_lane;
     float we_lane = xl.we_lane;  // (run mode: + the terminal hack, P0's stage N)
 
@@ -254,7 +266,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         for (int k = row; k <= N; k += 16) {
             ld(k + 16, nxt);
             if (mode == kModeRun && !path && r < 3) my_traj[k * 3 + r] = cur.tq;
-            const P0In<M> in = p0_stage_inputs<M>(P, lc, r, k, N, cur.x, cur.u, cur.xnext);
+            const P0In<M> in = p0_stage_inputs<M>(P, mp, lc, r, k, N, cur.x, cur.u, cur.xnext);
             float* const st = s_stg + SL::at(k, r);
             st[SL::ZBAR] = in.zb;
             st[SL::YREF] = cur.y;
@@ -297,7 +309,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     // constant rows of [B A] (rows >= NGV) from stage 0, before the sweep: lane v holds column v (gcol), lane
     // NU+xi holds row xi (grow), so the initial-iterate dynamics below need only NGV row sums
     float gcol[NX], grow[NV];
-    const_rows<M>(P, lc, r, xb, ub, gcol, grow);
+    const_rows<M>(P, mp, lc, r, xb, ub, gcol, grow);
     float dx = is_x ? x0_lane - XB(0, xi) : 0.0f;  // this lane's state delta at the current stage
     float sum_c0 = 0.0f;  // complementarity of the initial point (its mean sets the first SD target)
     // warm start: the previous multipliers (LL, LU) of the stage, prefetched one stage ahead
@@ -414,10 +426,10 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         lds_ld(0, cur);
         // RP: the stage's box from the table, one stage ahead beside the LDS reads (the only global loads of this loop)
         float2 box = make_float2(lo_b, hi_b), box_n = box;
-        if constexpr (RP) box = stage_box(sbx, 0, N);
+        if constexpr (RP) box = stage_box<MT>(sbx, 0, N);
         for (int k = 0; k <= N; k++) {
             lds_ld(k + 1, nxt);
-            if constexpr (RP) box_n = stage_box(sbx, k + 1, N);
+            if constexpr (RP) box_n = stage_box<MT>(sbx, k + 1, N);
             float g[NX];
 #pragma unroll
             for (int i = 0; i < NX; i++) g[i] = (i < NGV && k < N) ? cur.g[i < NGV ? i : 0] : 0.0f;
@@ -437,7 +449,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         auto load_p0 = [&](int k, Row& o) {
             load_row(k, o.xb, o.ub, o.tr);
             o.lp = load_l(k);
-            if constexpr (RP) o.bx = stage_box(sbx, k, N);
+            if constexpr (RP) o.bx = stage_box<MT>(sbx, k, N);
             o.yr = 0.0f;
             if (mode != kModeRun) {  // (unconditional load of a valid entry, then a select)
                 const int kk = k <= N ? k : N;
@@ -457,8 +469,8 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         rw[0].lp = load_l(0);
         rw[1].lp = load_l(1);
         if constexpr (RP) {
-            rw[0].bx = stage_box(sbx, 0, N);
-            rw[1].bx = stage_box(sbx, 1, N);
+            rw[0].bx = stage_box<MT>(sbx, 0, N);
+            rw[1].bx = stage_box<MT>(sbx, 1, N);
         }
         rw[0].yr = rw[1].yr = 0.0f;
         if (mode != kModeRun) {
@@ -480,7 +492,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                 float xn[NX], g[NX];
 #pragma unroll
                 for (int q = 0; q < NX; q++) { xn[q] = 0.0f; g[q] = 0.0f; }
-                if (k < N) rk4_column<M>(c.xb, c.ub, P, lv ? r : NU, xn, g);
+                if (k < N) rk4_column<M>(c.xb, c.ub, P, mp, lv ? r : NU, xn, g);
                 float zbar = 0.0f;
 #pragma unroll
                 for (int j = 0; j < NU; j++)
@@ -512,7 +524,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
     constexpr bool kMcol = M::kMcolForm;  // per model (nmpc_models.hpp)
 #endif
     GConst<M> gcs;  // the constant rows of [B A] as uniform operands of the column-form M block (m_block)
-    if constexpr (kMcol) gconst_load<M>(gcs, gcol);
+    if constexpr (kMcol && !MT) gconst_load<M>(gcs, gcol);
 
     STAMP(1);
     // infeasibility threshold of this robot: qp_infeas_lambda scaled by its largest weight (terminal hack included)
@@ -705,7 +717,10 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                 bool seq_pivots = true;
                 if constexpr (kMcol) {
                     double m11, m10;
-                    m_block<M>(Lr, pivot, m11, m10, pg, Gd, gcs);  // column form: uniform constant rows + 3 broadcast rows
+                    // column form: 3 broadcast rows + the constant rows as uniform operands, or (model table on) as
+                    // broadcasts from the team's own lanes
+                    if constexpr (MT) m_block_team<M>(Lr, pivot, m11, m10, pg, Gd);
+                    else m_block<M>(Lr, pivot, m11, m10, pg, Gd, gcs);
                     STAMPF(4);
                     if constexpr (NU == 2 && M::kPivotsUpFront) {
                         chol_input_2<NX>(Lr, pivot, m11, m10, r, fail);  // both pivots up front
@@ -1008,7 +1023,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
         }
     }
     __threadfence_block();
-    if (r == 0) write_outputs<M>(P, a, mode, inst, status, it_done, exit_res, x0);
+    if (r == 0) write_outputs<M>(P, a, mp, mode, inst, status, it_done, exit_res, x0);
 #undef XB
 #undef UBAR
 }
@@ -1038,15 +1053,17 @@ hipError_t launch_sqp_rti_team(const KParams& P, const KArgs& a, int mode, hipSt
     const int km = mode != kModeRun ? kModeSolve : (a.segs ? kModeRunPath : kModeRun);
     auto pick2 = [&](auto msc, auto sdc, auto spc) {
         constexpr bool ms = decltype(msc)::value, sd = decltype(sdc)::value, sp = decltype(spc)::value;
-        auto pick3 = [&](auto rpc) {
-            constexpr bool rp = decltype(rpc)::value;
-            if (km == kModeRunPath) go(k_sqp_rti_team<M, ms, sd, kModeRunPath, sp, rp>);
-            else if (km == kModeRun) go(k_sqp_rti_team<M, ms, sd, kModeRun, sp, rp>);
-            else go(k_sqp_rti_team<M, ms, sd, kModeSolve, sp, rp>);
+        auto pick3 = [&](auto rpc, auto mtc) {
+            constexpr bool rp = decltype(rpc)::value, mt = decltype(mtc)::value;
+            if (km == kModeRunPath) go(k_sqp_rti_team<M, ms, sd, kModeRunPath, sp, rp, mt>);
+            else if (km == kModeRun) go(k_sqp_rti_team<M, ms, sd, kModeRun, sp, rp, mt>);
+            else go(k_sqp_rti_team<M, ms, sd, kModeSolve, sp, rp, mt>);
         };
-        // the per-robot table and the stage table: instantiations of their own (sqp_steps.hpp lane_ctx, stage_box)
-        if (a.rparams || a.sbounds) pick3(std::true_type{});
-        else pick3(std::false_type{});
+        // the tables: instantiations of their own (sqp_steps.hpp lane_ctx, stage_box, robot_vals). The model table's
+        // read the other two as well
+        if (a.rmodel) pick3(std::true_type{}, std::true_type{});
+        else if (a.rparams || a.sbounds) pick3(std::true_type{}, std::false_type{});
+        else pick3(std::false_type{}, std::false_type{});
     };
     // record layout: tric always split, diff per launch (a.rec_split), omni4 and Mehrotra never
     auto pick = [&](auto msc, auto sdc) {

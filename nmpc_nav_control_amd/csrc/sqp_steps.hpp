@@ -6,6 +6,7 @@
 //
 //   step                                   team kernel                         row-parallel kernel
 //   lane_ctx         roles, weights, bounds  prologue                            prologue
+//   robot_vals       model parameters        prologue                            prologue
 //   load_x0          x0, x0_lane, we_lane    prologue                            prologue
 //   const_rows       gcol, grow              before P0's stage loop              after P0a's rounds
 //   stage_column, stage_dyn                  C1 (column), F0 / F1 (dyn)          phases B, C and the adjoint
@@ -88,6 +89,17 @@ __device__ __forceinline__ LaneCtx<M> lane_ctx(const KParams& P, const KArgs& a,
     return c;
 }
 
+// ---- the robot's model parameters (nmpc_models.hpp ModelPar): the handle's, or with the model table on
+// (KArgs::rmodel) the robot's column, NP loads here in the prologue (robot_vals; the kernels keep the values and hand
+// the functors a view of them). Every reader of the model parameters takes that view: P0's RK4 columns, const_rows,
+// load_x0's direct kinematics and write_outputs' inverse kinematics. A NaN or a zero in the column makes the robot's
+// dynamics NaN: it fails alone with status 1 ----
+template <class M>
+__device__ __forceinline__ ModelVals robot_vals(const KParams& P, const KArgs& a, int inst)
+{
+    return model_vals<M>(P, a.rmodel, (size_t)a.sstride, inst);
+}
+
 // ---- this lane's box at a stage (the stage table, KArgs::sbounds) ------------------------------------------------
 // lo / hi: the lane's pair of stage 0, ks: floats from one stage to the next. An input lane points at its lbu / ubu
 // row, a bounded state lane at its lbx / ubx row, every other lane at the robot's first row (a valid dummy, dropped).
@@ -95,17 +107,27 @@ __device__ __forceinline__ LaneCtx<M> lane_ctx(const KParams& P, const KArgs& a,
 // their reasons (a load under a lane mask, or a value selected behind a branch, turns the waits of P0's loop into full
 // drains). Stage table off and per-robot table on (the team kernel's RP instantiations serve both): the same loads
 // read the robot's column of the per-robot table with ks = 0, so that launch keeps one box for every stage.
+// FB (the team kernel's model-table instantiations, which serve every combination of the three tables): with both
+// bound tables off the loads read a dummy pair and stage_box returns the lane's own box fb = {lo_b, hi_b} by a select.
 struct StageBox {
     const float *lo, *hi;
     size_t ks;
+    bool use_fb;
+    float2 fb;
 };
-template <class M>
+template <class M, bool FB = false>
 __device__ __forceinline__ StageBox stage_box_ctx(const KArgs& a, int inst, const LaneCtx<M>& c, int r)
 {
     constexpr int NBX = M::NBX, NBU = M::NBU, SR = sb_rows(NBX, NBU);
     const int bj = c.is_u ? r : (c.cx >= 0 ? c.cx : 0);
     StageBox s;
-    if (a.sbounds) {
+    s.use_fb = false;
+    s.fb = make_float2(c.lo_b, c.hi_b);
+    if (FB && !a.sbounds && !a.rparams) {
+        s.lo = s.hi = a.scratch;  // (a valid address; the value is dropped)
+        s.ks = 0;
+        s.use_fb = true;
+    } else if (a.sbounds) {
         const int lo = (c.is_u ? sb_off(kSbLbu, NBX, NBU) : sb_off(kSbLbx, NBX, NBU)) + bj;
         const int hi = (c.is_u ? sb_off(kSbUbu, NBX, NBU) : sb_off(kSbUbx, NBX, NBU)) + bj;
         s.lo = a.sbounds + sb_at(0, lo, inst, a.sstride, SR);
@@ -120,11 +142,15 @@ __device__ __forceinline__ StageBox stage_box_ctx(const KArgs& a, int inst, cons
     }
     return s;
 }
-// {lo, hi} of stage k, k clamped to N (the rows past a field's last used stage are allocated and never interpreted)
+// {lo, hi} of stage k, k clamped to N (the rows past a field's last used stage are allocated and never interpreted).
+// FB as in stage_box_ctx: only those instantiations have the select
+template <bool FB = false>
 __device__ __forceinline__ float2 stage_box(const StageBox& s, int k, int N)
 {
     const size_t kk = (size_t)(k <= N ? k : N);
-    return make_float2(s.lo[kk * s.ks], s.hi[kk * s.ks]);
+    const float2 v = make_float2(s.lo[kk * s.ks], s.hi[kk * s.ks]);
+    if constexpr (FB) return s.use_fb ? s.fb : v;
+    else return v;
 }
 // fmaxf in bound_start would swallow a NaN bound, so a NaN in a bound the QP uses (bd) poisons that stage's gradient
 // entry gr: the robot then fails alone with status 1, as lane_ctx's NaN weight makes it
@@ -144,7 +170,7 @@ struct X0Lane {
 // (NMPCNavControlDiff.cpp:88-101); solve mode: the caller's x0
 template <class M, bool TBL = true>
 __device__ __forceinline__ X0Lane load_x0(const KParams& P, const KArgs& a, int mode, int inst, const LaneCtx<M>& c,
-                                          float (&x0)[M::NX])
+                                          const typename M::Par& mp, float (&x0)[M::NX])
 {
     constexpr int NX = M::NX;
     const size_t S = (size_t)a.stride, Bn = (size_t)a.B;
@@ -158,7 +184,7 @@ __device__ __forceinline__ X0Lane load_x0(const KParams& P, const KArgs& a, int 
         x0[1] = pose[1];
         x0[2] = pose[2];
         o.pose_th = pose[2];
-        M::direct_kin(vel, steer, P, x0 + 3);
+        M::direct_kin(vel, steer, mp, x0 + 3);
 #pragma unroll
         for (int i = 0; i < M::NBX; i++) x0[M::idxbx(i)] = a.carried[(size_t)i * S + inst];
     } else {
@@ -182,12 +208,13 @@ __device__ __forceinline__ X0Lane load_x0(const KParams& P, const KArgs& a, int 
 // ---- constant rows of [B A] (rows >= NGV) from stage 0's iterate row: lane v holds column v (gcol), lane NU+xi
 // holds row xi (grow), so the dynamics products need only NGV row sums ---------------------------------------------
 template <class M>
-__device__ __forceinline__ void const_rows(const KParams& P, const LaneCtx<M>& c, int r, const float (&xb)[M::NX],
-                                           const float (&ub)[M::NU], float (&gcol)[M::NX], float (&grow)[M::NX + M::NU])
+__device__ __forceinline__ void const_rows(const KParams& P, const typename M::Par& mp, const LaneCtx<M>& c, int r,
+                                           const float (&xb)[M::NX], const float (&ub)[M::NU], float (&gcol)[M::NX],
+                                           float (&grow)[M::NX + M::NU])
 {
     constexpr int NX = M::NX, NU = M::NU, NV = NX + NU, NGV = M::NGV;
     float xn0[NX], g0[NX];
-    rk4_column<M>(xb, ub, P, c.lv ? r : NU, xn0, g0);
+    rk4_column<M>(xb, ub, P, mp, c.lv ? r : NU, xn0, g0);
 #pragma unroll
     for (int i = 0; i < NX; i++) gcol[i] = (c.lv && i >= NGV) ? g0[i] : 0.0f;
     sfor<0, NV>([&](auto vc) {
@@ -244,8 +271,9 @@ struct P0In {
     float zb, bk, g[M::NX];
 };
 template <class M>
-__device__ __forceinline__ P0In<M> p0_stage_inputs(const KParams& P, const LaneCtx<M>& c, int r, int k, int N,
-                                                   const float (&x)[M::NX], const float (&u)[M::NU], float xnext)
+__device__ __forceinline__ P0In<M> p0_stage_inputs(const KParams& P, const typename M::Par& mp, const LaneCtx<M>& c,
+                                                   int r, int k, int N, const float (&x)[M::NX],
+                                                   const float (&u)[M::NU], float xnext)
 {
     constexpr int NX = M::NX, NU = M::NU;
     P0In<M> o;
@@ -254,7 +282,7 @@ __device__ __forceinline__ P0In<M> p0_stage_inputs(const KParams& P, const LaneC
     for (int i = 0; i < NX; i++) { xn[i] = 0.0f; o.g[i] = 0.0f; }
     o.bk = 0.0f;
     if (k < N) {
-        rk4_column<M>(x, u, P, c.lv ? r : NU, xn, o.g);
+        rk4_column<M>(x, u, P, mp, c.lv ? r : NU, xn, o.g);
 #pragma unroll
         for (int i = 0; i < NX; i++)
             if (c.is_x && c.xi == i) o.bk = xn[i] - xnext;
@@ -364,8 +392,9 @@ __device__ __forceinline__ void sqp_full_step(int N, bool is_x, float x0_lane, E
 // ---- the robot's outputs (one lane): u0, x1, status, iteration counts, warm tag, exit residuals, and in run mode the
 // carried refs and the command ---------------------------------------------------------------------------------
 template <class M>
-__device__ __forceinline__ void write_outputs(const KParams& P, const KArgs& a, int mode, int inst, int status,
-                                              int it_done, const float (&exit_res)[3], const float (&x0)[M::NX])
+__device__ __forceinline__ void write_outputs(const KParams& P, const KArgs& a, const typename M::Par& mp, int mode,
+                                              int inst, int status, int it_done, const float (&exit_res)[3],
+                                              const float (&x0)[M::NX])
 {
     constexpr int NX = M::NX, NU = M::NU;
     const size_t S = (size_t)a.stride, Bn = (size_t)a.B;
@@ -397,7 +426,7 @@ __device__ __forceinline__ void write_outputs(const KParams& P, const KArgs& a, 
             rr[i] = x0[M::idxbx(i)] + u0[i] * P.dt_ctrl;
             a.carried[(size_t)i * S + inst] = rr[i];
         }
-        M::inverse_kin(rr, P, cmd);
+        M::inverse_kin(rr, mp, cmd);
         if (a.cmd) {
 #pragma unroll
             for (int j = 0; j < 3; j++) a.cmd[(size_t)j * Bn + inst] = cmd[j];

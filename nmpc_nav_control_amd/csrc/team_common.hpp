@@ -122,9 +122,10 @@ __device__ __forceinline__ void mrow_pg_block(double (&acc)[NX + NU], double& md
 template <class M>
 constexpr int mcol_nbc() { return M::NGV > 3 ? M::NGV : 3; }
 
-// Constant entries of rows >= mcol_nbc of [B A] (M::gmask), identical for every robot of a launch (they depend on
-// the model parameters only, tests/test_oracle.py test_constant_jacobian_rows): read once per launch from lane r of
-// the wave's first team, so each is one uniform value (a scalar operand) for every lane
+// Constant entries of rows >= mcol_nbc of [B A] (M::gmask), identical for every robot of a launch whose model table
+// is off (they depend on dt and the model parameters only, tests/test_oracle.py test_constant_jacobian_rows): read
+// once per launch from lane r of the wave's first team, so each is one uniform value (a scalar operand) for every
+// lane. Launches with the model table on do not take this form (sqp_rti_team.hip MT)
 template <class M>
 struct GConst {
     double v[M::NX][M::NX + M::NU];
@@ -169,6 +170,34 @@ __device__ __forceinline__ void m_block(double (&Lr)[M::NX + M::NU], double& piv
         mcol_var_block_7_2_3(Lr, pivot, m11, m10, pg, gd);
     } else {
         mcol_var_block_11_4_3(Lr, pivot, pg, gd);
+        m11 = m10 = 0.0;
+    }
+}
+
+// m_block for launches whose robots have their own model parameters (the model table, sqp_rti_team.hip MT): the
+// constant entries of rows >= mcol_nbc differ between the four teams of a wave, so they cannot be wave-uniform
+// operands. The same structural-nonzero FMAs (diff and tric 10, omni4 20) take G[i][r] from lane r of the team's own
+// DPP row instead (gd[i] for i >= NGV is the team's gcol, widened to fp64 once before the IPM loop), fused into the
+// block of the three broadcast rows (team_asm_gen.hpp mcol_team_block_*). Per accumulator the terms come in m_block's
+// order, so a table that holds one p for a whole wave gives m_block's M bit for bit.
+template <class M>
+__device__ __forceinline__ void m_block_team(double (&Lr)[M::NX + M::NU], double& pivot, double& m11, double& m10,
+                                             const double (&pg)[M::NX], const double (&gd)[M::NX])
+{
+    constexpr int NX = M::NX, NU = M::NU;
+    static_assert(mcol_nbc<M>() == 3, "generated broadcast blocks cover three rows");
+    if constexpr (NX == 7 && NU == 2) {
+        static_assert(M::gmask(3) == mcol_team_mask_7_2(3) && M::gmask(4) == mcol_team_mask_7_2(4) &&
+                      M::gmask(5) == mcol_team_mask_7_2(5) && M::gmask(6) == mcol_team_mask_7_2(6),
+                      "tools/gen_team_asm.py CONST_ROWS follows the model's gmask");
+        mcol_team_block_7_2_3(Lr, pivot, m11, m10, pg, gd);
+    } else {
+        static_assert(M::gmask(3) == mcol_team_mask_11_4(3) && M::gmask(4) == mcol_team_mask_11_4(4) &&
+                      M::gmask(5) == mcol_team_mask_11_4(5) && M::gmask(6) == mcol_team_mask_11_4(6) &&
+                      M::gmask(7) == mcol_team_mask_11_4(7) && M::gmask(8) == mcol_team_mask_11_4(8) &&
+                      M::gmask(9) == mcol_team_mask_11_4(9) && M::gmask(10) == mcol_team_mask_11_4(10),
+                      "tools/gen_team_asm.py CONST_ROWS follows the model's gmask");
+        mcol_team_block_11_4_3(Lr, pivot, pg, gd);
         m11 = m10 = 0.0;
     }
 }
@@ -344,8 +373,8 @@ __device__ __forceinline__ int xcomp(int xi)
 // Column `col` (slot convention: col < NU input col, else state col - NU) of the RK4 map's sensitivity at
 // (x, u), propagated by one lane through the four stages, together with the nominal step xn.
 template <class M>
-__device__ __forceinline__ void rk4_column(const float* x, const float* u, const KParams& P, int col, float* xn,
-                                           float* g)
+__device__ __forceinline__ void rk4_column(const float* x, const float* u, const KParams& P,
+                                           const typename M::Par& mp, int col, float* xn, float* g)
 {
     constexpr int NX = M::NX, NU = M::NU;
     const float h = P.dt;
@@ -360,11 +389,11 @@ __device__ __forceinline__ void rk4_column(const float* x, const float* u, const
     const float wgt[4] = {1.0f, 2.0f, 2.0f, 1.0f};
 #pragma unroll
     for (int st = 0; st < 4; st++) {
-        M::f(xs, u, P, k);
+        M::f(xs, u, mp, k);
         float S1[NX][1], D1[NX][1];
 #pragma unroll
         for (int i = 0; i < NX; i++) S1[i][0] = s[i];
-        M::template jvp<1>(xs, S1, P, D1);  // Jx s (the input block of the models is [0; I] on the last NU rows)
+        M::template jvp<1>(xs, S1, mp, D1);  // Jx s (the input block of the models is [0; I] on the last NU rows)
         float dk[NX];
 #pragma unroll
         for (int i = 0; i < NX; i++) dk[i] = D1[i][0];

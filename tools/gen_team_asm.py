@@ -84,6 +84,52 @@ def mcol_var_block(nx, nu, ngv):
             f"        : {ins});\n}}\n")
 
 
+# structural nonzeros of the constant rows i >= 3 of [B A] over the columns [u | x] ('1'), per shape: diff2amr and
+# tric3amr share (7, 2) (wheel / speed and ref rows), omni4amr is (11, 4). The kernels check them against the models'
+# gmask (team_common.hpp m_block_team)
+CONST_ROWS = {
+    (7, 2): {3: "1....1.1.", 4: ".1....1.1", 5: "1......1.", 6: ".1......1"},
+    (11, 4): {3: "1......1...1...", 4: ".1......1...1..", 5: "..1......1...1.", 6: "...1......1...1",
+              7: "1..........1...", 8: ".1..........1..", 9: "..1..........1.", 10: "...1..........1"},
+}
+
+
+def mcol_team_block(nx, nu, ngv):
+    # mcol_var_block with the constant rows i >= ngv of [B A] as well, over their structural nonzeros only
+    # (CONST_ROWS: 10 FMAs for (7, 2), 20 for (11, 4)): acc[r] += bcast_r(Gd[i]) * pg[i], G[i][r] broadcast from lane r
+    # of the team's own row instead of a wave-uniform operand, for launches whose robots have their own model
+    # parameters (the model table). Per accumulator the terms come in m_block's order (constant rows, then the ngv
+    # broadcast rows), so with equal parameters in a wave the result is m_block's bit for bit.
+    # Operands: acc 0..nv-1 (+v), md0 [m11 m10] (=v), Gd 0..nx-1, pg 0..nx-1
+    nv = nx + nu
+    npv = 3 if nu == 2 else 1
+    g0, p0 = nv + npv, nv + npv + nx
+    rows = CONST_ROWS[(nx, nu)]
+    lines = ["s_nop 1"]
+    for i in sorted(rows):
+        for r in range(nv):
+            if rows[i][r] == "1":
+                lines.append(f"v_fmac_f64_dpp %{r}, %{g0 + i}, %{p0 + i} row_newbcast:{r}{M}")
+    for i in range(ngv):
+        for r in range(nv):
+            lines.append(f"v_fmac_f64_dpp %{r}, %{g0 + i}, %{p0 + i} row_newbcast:{r}{M}")
+    lines.append("s_nop 1")
+    lines.append(f"v_mov_b64_dpp %{nv}, %0 row_newbcast:0{M}")
+    if npv == 3:
+        lines.append(f"v_mov_b64_dpp %{nv + 1}, %1 row_newbcast:1{M}")
+        lines.append(f"v_mov_b64_dpp %{nv + 2}, %0 row_newbcast:1{M}")
+    outs = ", ".join([f'"+v"(acc[{r}])' for r in range(nv)] + ['"=&v"(md0)'] +
+                     (['"=&v"(m11)', '"=&v"(m10)'] if npv == 3 else []))
+    ins = ", ".join([f'"v"(gd[{i}])' for i in range(nx)] + [f'"v"(pg[{i}])' for i in range(nx)])
+    body = "\\n\\t".join(lines)
+    extra = ", double& m11, double& m10" if npv == 3 else ""
+    masks = " : ".join(f"i == {i} ? {sum(1 << r for r in range(nv) if rows[i][r] == '1')}u" for i in sorted(rows))
+    return (f"__host__ __device__ constexpr unsigned mcol_team_mask_{nx}_{nu}(int i) {{ return {masks} : 0u; }}\n"
+            f"__device__ __forceinline__ void mcol_team_block_{nx}_{nu}_{ngv}(double (&acc)[{nv}], double& md0{extra},"
+            f" const double (&pg)[{nx}], const double (&gd)[{nx}])\n{{\n    asm(\"{body}\"\n        : {outs}\n"
+            f"        : {ins});\n}}\n")
+
+
 def chol_update(nx, nu):
     # column j done: Lr[jp] -= bcast_jp(lj) * lj for jp > j, then pivot of column j+1 = bcast_{j+1}(Lr[j+1])
     nv = nx + nu
@@ -245,6 +291,7 @@ def generate():
     for nx, nu in SHAPES:
         nv = nx + nu
         parts += [pg_block(nx, nu), mrow_pg_block(nx, nu)] + [mcol_var_block(nx, nu, g) for g in VAR_ROWS[(nx, nu)]]
+        parts += [mcol_team_block(nx, nu, g) for g in VAR_ROWS[(nx, nu)]]
         parts += [chol_update(nx, nu),
                   dot_f32(nx, nu, f"dot_x_{nx}_{nu}"), dot_f32(nv, 0, f"dot_v_{nx}_{nu}"),
                   mst_rowmul(nx, nu), mst_rowmul_lt(nx, nu), mst_rowdot(nx, nu), mst_chol(nx, nu), mst_trsv(nx, nu), mst_vdot(nx, nu)]
