@@ -184,13 +184,9 @@ class BatchSolver:
         (n = nbx, nbx, nbu, nbu, ny, nx) or None (those rows stay); mask uint8 [B] selects the robots (None: all).
         One launch on the stream; from then on every launch of this solver takes each robot's values from the table
         (until clear_robot_params)."""
-        rows = dict(lbx=(lbx, self.nbx), ubx=(ubx, self.nbx), lbu=(lbu, self.nbu), ubu=(ubu, self.nbu),
-                    W=(W, self.ny), W_e=(W_e, self.nx))
-        given = [t for t, _ in rows.values() if t is not None]
-        if not given:
-            raise ValueError("set_robot_params: no field given")
-        B = self._batch_of(given[0])
-        rp = RobotParamsStruct(**{k: _ptr(t, F32, (n, B), k) for k, (t, n) in rows.items()})
+        given = dict(lbx=lbx, ubx=ubx, lbu=lbu, ubu=ubu, W=W, W_e=W_e)
+        B = self._batch_given(given, 1, "set_robot_params: no field given")
+        rp = RobotParamsStruct(**{k: _ptr(given[k], F32, (n, B), k) for k, n in self._rp_fields()})
         check(lib().nmpc_batch_set_robot_params(self._h, B, ctypes.byref(rp), _ptr(mask, U8, (B,), "mask"),
                                                 _stream(stream)), "nmpc_batch_set_robot_params")
 
@@ -199,12 +195,7 @@ class BatchSolver:
         """The batched nmpc_model_params_set_limits (nmpc_batch_set_robot_limits): float32 device tensors [B], each
         optional; the steering ones are read for tric only. mask as set_robot_params."""
         arrs = dict(v_max=v_max, a_max=a_max, alpha_min=alpha_min, alpha_max=alpha_max, dalpha_max=dalpha_max)
-        given = [t for t in arrs.values() if t is not None]
-        if not given:
-            raise ValueError("set_robot_limits: no limit given")
-        B = given[0].shape[0]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
+        B = self._batch_given(arrs, 0, "set_robot_limits: no limit given")
         check(lib().nmpc_batch_set_robot_limits(self._h, B, *[_ptr(t, F32, (B,), k) for k, t in arrs.items()],
                                                 _ptr(mask, U8, (B,), "mask"), _stream(stream)),
               "nmpc_batch_set_robot_limits")
@@ -212,10 +203,7 @@ class BatchSolver:
     def robot_params(self):
         """View of the per-robot table [rows][cap] (rows lbx ubx lbu ubu W W_e), or None while it is off
         (nmpc_batch_robot_params)."""
-        tb, rows, stride = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
-        check(lib().nmpc_batch_robot_params(self._h, ctypes.byref(tb), ctypes.byref(rows), ctypes.byref(stride)),
-              "nmpc_batch_robot_params")
-        return _DeviceView(tb.value, (rows.value, stride.value), self.device) if tb.value else None
+        return self._table_view("nmpc_batch_robot_params")
 
     def clear_robot_params(self):
         """Turn the per-robot table off: launches use the handle's parameters again."""
@@ -229,11 +217,8 @@ class BatchSolver:
         N = self.N
         rows = dict(lbx=(lbx, N + 1, self.nbx), ubx=(ubx, N + 1, self.nbx), lbu=(lbu, N, self.nbu),
                     ubu=(ubu, N, self.nbu))
-        given = [t for t, _, _ in rows.values() if t is not None]
-        if not given:
-            raise ValueError("set_stage_bounds: no field given")
-        B = self._batch_last(given[0])
-        sb = StageBoundsStruct(**{k: _ptr(t, F32, (ns, n, B), k) for k, (t, ns, n) in rows.items()})
+        B = self._batch_given({k: r[0] for k, r in rows.items()}, -1, "set_stage_bounds: no field given")
+        sb =StageBoundsStruct(**{k: _ptr(t, F32, (ns, n, B), k) for k, (t, ns, n) in rows.items()})
         check(lib().nmpc_batch_set_stage_bounds(self._h, B, ctypes.byref(sb), _ptr(mask, U8, (B,), "mask"),
                                                 _stream(stream)), "nmpc_batch_set_stage_bounds")
 
@@ -245,10 +230,7 @@ class BatchSolver:
         N = self.N
         arrs = dict(v_max=(v_max, N + 1), a_max=(a_max, N), alpha_min=(alpha_min, N + 1), alpha_max=(alpha_max, N + 1),
                     dalpha_max=(dalpha_max, N))
-        given = [t for t, _ in arrs.values() if t is not None]
-        if not given:
-            raise ValueError("set_stage_limits: no limit given")
-        B = self._batch_last(given[0])
+        B = self._batch_given({k: r[0] for k, r in arrs.items()}, -1, "set_stage_limits: no limit given")
         check(lib().nmpc_batch_set_stage_limits(self._h, B, *[_ptr(t, F32, (ns, B), k) for k, (t, ns) in arrs.items()],
                                                 _ptr(mask, U8, (B,), "mask"), _stream(stream)),
               "nmpc_batch_set_stage_limits")
@@ -265,9 +247,7 @@ class BatchSolver:
     def stage_bounds(self):
         """View of the stage table as opaque bytes [1][bytes] (uint8), or None while it is off
         (nmpc_batch_stage_bounds)."""
-        tb, nb = ctypes.c_void_p(), ctypes.c_size_t()
-        check(lib().nmpc_batch_stage_bounds(self._h, ctypes.byref(tb), ctypes.byref(nb)), "nmpc_batch_stage_bounds")
-        return _DeviceView(tb.value, (1, nb.value), self.device, torch.uint8) if tb.value else None
+        return self._table_view("nmpc_batch_stage_bounds", opaque=True)
 
     def clear_stage_bounds(self):
         """Turn the stage table off: launches use one box per robot again."""
@@ -285,10 +265,7 @@ class BatchSolver:
 
     def robot_model(self):
         """View of the model table [np][cap], or None while it is off (nmpc_batch_robot_model)."""
-        tb, rows, stride = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
-        check(lib().nmpc_batch_robot_model(self._h, ctypes.byref(tb), ctypes.byref(rows), ctypes.byref(stride)),
-              "nmpc_batch_robot_model")
-        return _DeviceView(tb.value, (rows.value, stride.value), self.device) if tb.value else None
+        return self._table_view("nmpc_batch_robot_model")
 
     def clear_robot_model(self):
         """Turn the model table off: launches use the handle's p again."""
@@ -299,64 +276,82 @@ class BatchSolver:
         tensors), then the per-robot table as a tensor when it is on, then the stage table as
         {"stage_bounds": bytes} and the model table as {"robot_model": tensor} when they are on."""
         saved = [v.to_tensor() for v in self.state() + self.warm_state()]
-        rp = self.robot_params()
-        if rp is not None:
-            saved.append(rp.to_tensor())
-        sb = self.stage_bounds()
-        if sb is not None:
-            saved.append({"stage_bounds": sb.to_tensor()})
-        rm = self.robot_model()
-        if rm is not None:
-            saved.append({"robot_model": rm.to_tensor()})
+        for name, view, _, _ in self._tables():
+            v = view()
+            if v is not None:
+                saved.append(v.to_tensor() if name is None else {name: v.to_tensor()})
         return saved
 
     def restore_state(self, saved):
         for v, t in zip(self.state() + self.warm_state(), saved):
             v.copy_from(t)
-        stage = [e["stage_bounds"] for e in saved[5:] if isinstance(e, dict) and "stage_bounds" in e]
-        model = [e["robot_model"] for e in saved[5:] if isinstance(e, dict) and "robot_model" in e]
-        saved = [e for e in saved if not isinstance(e, dict)]
-        if model:
-            # the table's columns, written through the writer (which allocates and switches the table on)
-            self.set_robot_model(model[0].to(self.device).contiguous())
-            torch.cuda.synchronize()
-        else:
-            self.clear_robot_model()
-        if stage:
-            # (a shift by no stage allocates the table and switches it on; the bytes then replace its first fill)
-            self.shift_stage_bounds(0)
-            self.stage_bounds().copy_from(stage[0])
-        else:
-            self.clear_stage_bounds()
-        if len(saved) > 5:
-            # the table's rows, written through the writer (which allocates and switches the table on)
-            t = saved[5].to(self.device)
+        # every table as the checkpoint has it: loaded when it is there, else switched off. The model table first, the
+        # per-robot table last (the stage table's bytes replace its first fill, whatever that took from the latter)
+        have = {}
+        for e in saved[5:]:
+            have.update(e if isinstance(e, dict) else {None: e})
+        for name, _, load, clear in reversed(self._tables()):
+            if name in have:
+                load(have[name].to(self.device))
+                torch.cuda.synchronize()
+            else:
+                clear()
+
+    def _tables(self):
+        """The per-robot device tables in save_state's order: the key of the table's entry in a checkpoint (None: a
+        bare tensor), its view, how a saved copy is loaded (through a writer, which allocates the table and switches
+        it on) and how it is switched off."""
+        def load_params(t):
             cuts, off = {}, 0
-            for k, n in (("lbx", self.nbx), ("ubx", self.nbx), ("lbu", self.nbu), ("ubu", self.nbu), ("W", self.ny),
-                         ("W_e", self.nx)):
+            for k, n in self._rp_fields():
                 cuts[k] = t[off:off + n].contiguous()
                 off += n
             self.set_robot_params(**cuts)
-            torch.cuda.synchronize()
+
+        def load_stage(t):
+            self.shift_stage_bounds(0)  # (a shift by no stage is the writer that writes nothing)
+            self.stage_bounds().copy_from(t)
+
+        return [(None, self.robot_params, load_params, self.clear_robot_params),
+                ("stage_bounds", self.stage_bounds, load_stage, self.clear_stage_bounds),
+                ("robot_model", self.robot_model, lambda t: self.set_robot_model(t.contiguous()),
+                 self.clear_robot_model)]
+
+    def _rp_fields(self):
+        """the per-robot table's fields and their rows, in the table's order"""
+        return (("lbx", self.nbx), ("ubx", self.nbx), ("lbu", self.nbu), ("ubu", self.nbu), ("W", self.ny),
+                ("W_e", self.nx))
+
+    def _table_view(self, fn, opaque=False):
+        """View of a device table through its C view function, or None while the table is off: [rows][cap] float32, or
+        (opaque) the table's bytes [1][bytes] uint8."""
+        tb = ctypes.c_void_p()
+        if opaque:
+            nb = ctypes.c_size_t()
+            check(getattr(lib(), fn)(self._h, ctypes.byref(tb), ctypes.byref(nb)), fn)
+            shape, dtype = (1, nb.value), torch.uint8
         else:
-            self.clear_robot_params()
+            rows, stride = ctypes.c_int(), ctypes.c_int()
+            check(getattr(lib(), fn)(self._h, ctypes.byref(tb), ctypes.byref(rows), ctypes.byref(stride)), fn)
+            shape, dtype = (rows.value, stride.value), torch.float32
+        return _DeviceView(tb.value, shape, self.device, dtype) if tb.value else None
 
     def empty(self, *shape, dtype=torch.float32):
         return torch.empty(*shape, dtype=dtype, device=self.device)
 
-    def _batch_of(self, t):
-        """B of a call, from its first [field][B] input."""
-        B = t.shape[1]
+    def _batch_of(self, t, axis=1):
+        """B of a call, from its first input: axis 1 of a [field][B] tensor, or the axis given."""
+        B = t.shape[axis]
         if not 0 <= B <= self.capacity:
             raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
         return B
 
-    def _batch_last(self, t):
-        """B of a stage-table call, from the last dimension of its first input."""
-        B = t.shape[-1]
-        if not 0 <= B <= self.capacity:
-            raise ValueError(f"batch {B} exceeds the capacity {self.capacity}")
-        return B
+    def _batch_given(self, fields, axis, none_msg):
+        """B of a table writer whose fields (name -> tensor or None) are each optional, from the first one given."""
+        given = [t for t in fields.values() if t is not None]
+        if not given:
+            raise ValueError(none_msg)
+        return self._batch_of(given[0], axis)
 
     def _outputs(self, B, cmd, u0, status, qp_iter, qp_res, stream):
         """The trailing arguments of every run-mode entry point: the per-robot outputs and the stream."""

@@ -15,6 +15,16 @@
 
 using namespace nmpc;
 
+// One per-robot device table of a handle (DESIGN.md "Per-robot device tables"): off until its first writer, which
+// allocates it and fills it with what the launches used until then (table_ready); nmpc_batch_clear_* switches it off
+// and keeps the allocation for the next writer, which refills it
+struct DevTable {
+    float* p = nullptr;
+    size_t floats = 0;  // its size, fixed at create
+    bool on = false;    // launches read it
+    float* view() const { return on ? p : nullptr; }  // what launches and the view functions see
+};
+
 struct nmpc_batch {
     nmpc_model_params prm;
     KParams kp;
@@ -59,20 +69,13 @@ struct nmpc_batch {
     unsigned char* node_active = nullptr;
     int* node_n = nullptr;
     int* node_status = nullptr;
-    // per-robot bounds and weights (nmpc_batch_set_robot_params): the table [rp.off[kRpFields]][capacity], allocated
-    // by the first writer; rp_on: launches read it (resident_args)
-    float* rparams = nullptr;
+    // the per-robot device tables, read by the launches (resident_args) while they are on:
+    // bounds and weights (nmpc_batch_set_robot_params), [rp.off[kRpFields]][capacity];
+    // stage-varying bounds (nmpc_batch_set_stage_bounds), (N + 1) * sb_rows * capacity floats (sb_at, nmpc_kernels.hpp);
+    // model parameters (nmpc_batch_set_robot_model), [np][capacity], which the harness plant reads too (fleet_sim)
+    DevTable rparams, sbounds, rmodel;
     RpRows rp{};
-    bool rp_on = false;
-    // stage-varying bounds (nmpc_batch_set_stage_bounds): the stage table, (N + 1) * sb_rows * capacity floats (sb_at,
-    // nmpc_kernels.hpp), allocated by the first writer; sb_on: launches read it (resident_args)
-    float* sbounds = nullptr;
-    bool sb_on = false;
-    // per-robot model parameters (nmpc_batch_set_robot_model): the model table [np][capacity], allocated by the first
-    // writer; rm_on: launches and the harness plant read it (resident_args, fleet_sim)
-    float* rmodel = nullptr;
     int np = 0;
-    bool rm_on = false;
 };
 
 namespace {
@@ -335,22 +338,31 @@ KArgs resident_args(const nmpc_batch* b, int B)
     a.ubar = b->ubar;
     a.carried = b->carried;
     a.scratch = b->scratch;
-    if (b->rp_on) a.rparams = b->rparams;
-    if (b->sb_on) a.sbounds = b->sbounds;
-    if (b->rm_on) a.rmodel = b->rmodel;
+    a.rparams = b->rparams.view();
+    a.sbounds = b->sbounds.view();
+    a.rmodel = b->rmodel.view();
     return a;
 }
 
-// The per-robot table ready for a writer on stream s: allocated at the first call, and when it was off filled with
-// the handle's own parameters (KParams' fp32 values, so a table nobody wrote to solves what the handle solves)
-int rp_table(nmpc_batch* b, hipStream_t s)
+// A table ready for a writer on stream s: allocated at the first call and, whenever it was off, filled by fill(table)
+// (one launch on s) with what the launches used until now, so a table nobody wrote to solves what the handle solved.
+// It is on only if that launch succeeded
+template <class Fill>
+int table_ready(DevTable& t, const char* what, Fill&& fill)
 {
-    if (b->rp_on) return NMPC_OK;
-    const int rows = b->rp.off[kRpFields];
-    if (!b->rparams) {
-        const hipError_t e = hipMalloc(&b->rparams, sizeof(float) * (size_t)rows * (size_t)b->capacity);
+    if (t.on) return NMPC_OK;
+    if (!t.p) {
+        const hipError_t e = hipMalloc(&t.p, sizeof(float) * t.floats);
         if (e != hipSuccess) return hip_err(e, "hipMalloc");
     }
+    const int rc = hip_err(fill(t.p), what);
+    if (rc == NMPC_OK) t.on = true;
+    return rc;
+}
+
+// the handle's own column of the per-robot table (KParams' fp32 values); its first sb_rows rows are the stage table's
+RpColumn own_column(const nmpc_batch* b)
+{
     RpColumn col;
     std::memset(&col, 0, sizeof(col));
     const KParams& k = b->kp;
@@ -358,58 +370,74 @@ int rp_table(nmpc_batch* b, hipStream_t s)
     for (int i = 0; i < b->nbu; i++) { col.v[b->rp.off[kRpLbu] + i] = k.lbu[i]; col.v[b->rp.off[kRpUbu] + i] = k.ubu[i]; }
     for (int i = 0; i < b->ny; i++) col.v[b->rp.off[kRpW] + i] = k.W[i];
     for (int i = 0; i < b->nx; i++) col.v[b->rp.off[kRpWe] + i] = k.We[i];
-    const int rc = hip_err(launch_rp_fill(b->rparams, b->capacity, rows, col, s), "robot_params fill launch");
-    if (rc == NMPC_OK) b->rp_on = true;
-    return rc;
+    return col;
 }
 
-// The model table ready for a writer on stream s: allocated at the first call, and when it was off filled with the
-// handle's own p (KParams' fp32 values)
+int rp_table(nmpc_batch* b, hipStream_t s)
+{
+    return table_ready(b->rparams, "robot_params fill launch", [&](float* t) {
+        return launch_rows_fill(t, b->capacity, b->rp.off[kRpFields], own_column(b), s);
+    });
+}
+
 int rm_table(nmpc_batch* b, hipStream_t s)
 {
-    if (b->rm_on) return NMPC_OK;
-    if (!b->rmodel) {
-        const hipError_t e = hipMalloc(&b->rmodel, sizeof(float) * (size_t)b->np * (size_t)b->capacity);
-        if (e != hipSuccess) return hip_err(e, "hipMalloc");
-    }
-    RmColumn col{};
-    for (int i = 0; i < b->np; i++) col.v[i] = b->kp.p[i];
-    const int rc = hip_err(launch_rm_fill(b->rmodel, b->capacity, b->np, col, s), "robot_model fill launch");
-    if (rc == NMPC_OK) b->rm_on = true;
-    return rc;
+    return table_ready(b->rmodel, "robot_model fill launch", [&](float* t) {
+        RpColumn col{};
+        for (int i = 0; i < b->np; i++) col.v[i] = b->kp.p[i];
+        return launch_rows_fill(t, b->capacity, b->np, col, s);
+    });
 }
 
 SbDims sb_dims(const nmpc_batch* b) { return SbDims{b->prm.N, b->capacity, b->nbx, b->nbu}; }
-size_t sb_bytes(const nmpc_batch* b)
-{
-    return sizeof(float) * (size_t)(b->prm.N + 1) * (size_t)sb_rows(b->nbx, b->nbu) * (size_t)b->capacity;
-}
 
-// The stage table ready for a writer on stream s: allocated at the first call, and when it was off filled at every
-// stage with the box the launches used until now (the robot's column of the per-robot table if that is on, else the
-// handle's fp32 values)
+// the stage table's fill: at every stage the box the launches used until now (the robot's column of the per-robot
+// table if that is on, else the handle's)
 int sb_table(nmpc_batch* b, hipStream_t s)
 {
-    if (b->sb_on) return NMPC_OK;
-    if (!b->sbounds) {
-        const hipError_t e = hipMalloc(&b->sbounds, sb_bytes(b));
-        if (e != hipSuccess) return hip_err(e, "hipMalloc");
-    }
-    RpColumn col;
-    std::memset(&col, 0, sizeof(col));
-    const KParams& k = b->kp;
-    for (int i = 0; i < b->nbx; i++) {
-        col.v[sb_off(kSbLbx, b->nbx, b->nbu) + i] = k.lbx[i];
-        col.v[sb_off(kSbUbx, b->nbx, b->nbu) + i] = k.ubx[i];
-    }
-    for (int i = 0; i < b->nbu; i++) {
-        col.v[sb_off(kSbLbu, b->nbx, b->nbu) + i] = k.lbu[i];
-        col.v[sb_off(kSbUbu, b->nbx, b->nbu) + i] = k.ubu[i];
-    }
-    const int rc = hip_err(launch_sb_fill(b->sbounds, sb_dims(b), col, b->rp_on ? b->rparams : nullptr, b->rp, s),
-                           "stage_bounds fill launch");
-    if (rc == NMPC_OK) b->sb_on = true;
-    return rc;
+    return table_ready(b->sbounds, "stage_bounds fill launch", [&](float* t) {
+        return launch_sb_fill(t, sb_dims(b), own_column(b), b->rparams.view(), b->rp, s);
+    });
+}
+
+// A table's writer entry point: the checks every one of them makes, in their order (those that need no handle first;
+// bad: the failed check of the writer's own payload, or nullptr), the table ready on the stream, then the writer's
+// one launch
+template <class Write>
+int table_write(nmpc_batch* b, int B, const char* bad, int (*ready)(nmpc_batch*, hipStream_t), void* stream,
+                const char* what, Write&& write)
+{
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (bad) return set_err(NMPC_ERR_ARG, bad);
+    if (const int rc = check_batch(b, B)) return rc;
+    if (B == 0) return NMPC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = ready(b, s)) return rc;
+    return hip_err(write(s), what);
+}
+
+// the payload check of the two limits writers: msg when every array is NULL
+const char* no_limits(const float* v_max, const float* a_max, const float* alpha_min, const float* alpha_max,
+                      const float* dalpha_max, const char* msg)
+{
+    return (!v_max && !a_max && !alpha_min && !alpha_max && !dalpha_max) ? msg : nullptr;
+}
+
+// nmpc_batch_robot_params / nmpc_batch_robot_model: the view of a row-major table, [rows][capacity]
+int rows_view(nmpc_batch* b, DevTable nmpc_batch::*t, float** table, int* rows, int* stride)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (table) *table = (b->*t).view();
+    if (rows) *rows = (int)((b->*t).floats / (size_t)b->capacity);
+    if (stride) *stride = b->capacity;
+    return NMPC_OK;
+}
+
+int table_clear(nmpc_batch* b, DevTable nmpc_batch::*t)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    (b->*t).on = false;  // (the allocation stays for the next writer, which refills it)
+    return NMPC_OK;
 }
 
 // ... with the inputs and outputs every run-mode launch has; the reference (traj or the path march) is the caller's
@@ -574,6 +602,9 @@ int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** o
     b->ny = b->nx + b->nu;
     b->kp = to_kparams(*prm, b->nx, b->nu, b->nbx, b->nbu);
     b->rp = rp_rows(b->nx, b->nu, b->nbx, b->nbu);
+    b->rparams.floats = (size_t)b->rp.off[kRpFields] * (size_t)capacity;
+    b->sbounds.floats = (size_t)(prm->N + 1) * (size_t)sb_rows(b->nbx, b->nbu) * (size_t)capacity;
+    b->rmodel.floats = (size_t)b->np * (size_t)capacity;
     if (const char* sv = std::getenv("NMPC_AMD_SCHED")) {  // off | auto | sorted | interleaved
         const char* names[5] = {"off", "auto", "sorted", "interleaved", "spread"};
         for (int i = 0; i < 5; i++)
@@ -638,9 +669,7 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->node_active);
     (void)hipFree(b->node_n);
     (void)hipFree(b->node_status);
-    (void)hipFree(b->rparams);
-    (void)hipFree(b->sbounds);
-    (void)hipFree(b->rmodel);
+    for (const DevTable* t : {&b->rparams, &b->sbounds, &b->rmodel}) (void)hipFree(t->p);
     delete b;
     return NMPC_OK;
 }
@@ -999,134 +1028,89 @@ int nmpc_batch_forget_warm(nmpc_batch* b, int B, const unsigned char* mask, void
 int nmpc_batch_set_robot_params(nmpc_batch* b, int B, const nmpc_robot_params* rp, const unsigned char* mask,
                                 void* stream)
 {
-    // the checks that need no handle come first
-    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
-    if (!rp) return set_err(NMPC_ERR_ARG, "robot params is NULL");
-    if (!rp->lbx && !rp->ubx && !rp->lbu && !rp->ubu && !rp->W && !rp->W_e)
-        return set_err(NMPC_ERR_ARG, "robot params: every field is NULL");
-    if (const int rc = check_batch(b, B)) return rc;
-    if (B == 0) return NMPC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (const int rc = rp_table(b, s)) return rc;
-    return hip_err(launch_rp_set(b->rparams, b->capacity, B, b->rp, *rp, mask, s), "robot_params launch");
+    const char* bad = !rp ? "robot params is NULL"
+                      : (!rp->lbx && !rp->ubx && !rp->lbu && !rp->ubu && !rp->W && !rp->W_e)
+                          ? "robot params: every field is NULL"
+                          : nullptr;
+    return table_write(b, B, bad, rp_table, stream, "robot_params launch", [&](hipStream_t s) {
+        const float* const fields[kRpFields] = {rp->lbx, rp->ubx, rp->lbu, rp->ubu, rp->W, rp->W_e};
+        return launch_rows_set<kRpFields>(b->rparams.p, b->capacity, B, b->rp.off, fields, mask, s);
+    });
 }
 
 int nmpc_batch_set_robot_limits(nmpc_batch* b, int B, const float* v_max, const float* a_max, const float* alpha_min,
                                 const float* alpha_max, const float* dalpha_max, const unsigned char* mask,
                                 void* stream)
 {
-    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
-    if (!v_max && !a_max && !alpha_min && !alpha_max && !dalpha_max)
-        return set_err(NMPC_ERR_ARG, "robot limits: every array is NULL");
-    if (const int rc = check_batch(b, B)) return rc;
-    if (B == 0) return NMPC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (const int rc = rp_table(b, s)) return rc;
-    return hip_err(launch_rp_limits(b->rparams, b->capacity, B, b->rp, b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0,
-                                    v_max, a_max, alpha_min, alpha_max, dalpha_max, mask, s),
-                   "robot_limits launch");
+    const char* bad = no_limits(v_max, a_max, alpha_min, alpha_max, dalpha_max, "robot limits: every array is NULL");
+    return table_write(b, B, bad, rp_table, stream, "robot_limits launch", [&](hipStream_t s) {
+        return launch_rp_limits(b->rparams.p, b->capacity, B, b->rp, b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0, v_max,
+                                a_max, alpha_min, alpha_max, dalpha_max, mask, s);
+    });
 }
 
 int nmpc_batch_robot_params(nmpc_batch* b, float** table, int* rows, int* stride)
 {
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (table) *table = b->rp_on ? b->rparams : nullptr;
-    if (rows) *rows = b->rp.off[kRpFields];
-    if (stride) *stride = b->capacity;
-    return NMPC_OK;
+    return rows_view(b, &nmpc_batch::rparams, table, rows, stride);
 }
 
-int nmpc_batch_clear_robot_params(nmpc_batch* b)
-{
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    b->rp_on = false;  // (the allocation stays for the next writer, which refills it)
-    return NMPC_OK;
-}
+int nmpc_batch_clear_robot_params(nmpc_batch* b) { return table_clear(b, &nmpc_batch::rparams); }
 
 int nmpc_batch_set_stage_bounds(nmpc_batch* b, int B, const nmpc_stage_bounds* sb, const unsigned char* mask,
                                 void* stream)
 {
-    // the checks that need no handle come first
-    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
-    if (!sb) return set_err(NMPC_ERR_ARG, "stage bounds is NULL");
-    if (!sb->lbx && !sb->ubx && !sb->lbu && !sb->ubu)
-        return set_err(NMPC_ERR_ARG, "stage bounds: every field is NULL");
-    if (const int rc = check_batch(b, B)) return rc;
-    if (B == 0) return NMPC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (const int rc = sb_table(b, s)) return rc;
-    return hip_err(launch_sb_set(b->sbounds, sb_dims(b), B, *sb, mask, s), "stage_bounds launch");
+    const char* bad = !sb ? "stage bounds is NULL"
+                      : (!sb->lbx && !sb->ubx && !sb->lbu && !sb->ubu) ? "stage bounds: every field is NULL"
+                                                                       : nullptr;
+    return table_write(b, B, bad, sb_table, stream, "stage_bounds launch", [&](hipStream_t s) {
+        return launch_sb_set(b->sbounds.p, sb_dims(b), B, *sb, mask, s);
+    });
 }
 
 int nmpc_batch_set_stage_limits(nmpc_batch* b, int B, const float* v_max, const float* a_max, const float* alpha_min,
                                 const float* alpha_max, const float* dalpha_max, const unsigned char* mask,
                                 void* stream)
 {
-    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
-    if (!v_max && !a_max && !alpha_min && !alpha_max && !dalpha_max)
-        return set_err(NMPC_ERR_ARG, "stage limits: every array is NULL");
-    if (const int rc = check_batch(b, B)) return rc;
-    if (B == 0) return NMPC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (const int rc = sb_table(b, s)) return rc;
-    return hip_err(launch_sb_limits(b->sbounds, sb_dims(b), B, b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0, v_max,
-                                    a_max, alpha_min, alpha_max, dalpha_max, mask, s),
-                   "stage_limits launch");
+    const char* bad = no_limits(v_max, a_max, alpha_min, alpha_max, dalpha_max, "stage limits: every array is NULL");
+    return table_write(b, B, bad, sb_table, stream, "stage_limits launch", [&](hipStream_t s) {
+        return launch_sb_limits(b->sbounds.p, sb_dims(b), B, b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0, v_max, a_max,
+                                alpha_min, alpha_max, dalpha_max, mask, s);
+    });
 }
 
 int nmpc_batch_shift_stage_bounds(nmpc_batch* b, int B, int n, const unsigned char* mask, void* stream)
 {
-    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
-    if (n < 0) return set_err(NMPC_ERR_ARG, "stage shift: n must be >= 0");
-    if (const int rc = check_batch(b, B)) return rc;
-    if (B == 0) return NMPC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (const int rc = sb_table(b, s)) return rc;
-    return hip_err(launch_sb_shift(b->sbounds, sb_dims(b), B, n, mask, s), "stage_shift launch");
+    const char* bad = n < 0 ? "stage shift: n must be >= 0" : nullptr;
+    return table_write(b, B, bad, sb_table, stream, "stage_shift launch",
+                       [&](hipStream_t s) { return launch_sb_shift(b->sbounds.p, sb_dims(b), B, n, mask, s); });
 }
 
 int nmpc_batch_stage_bounds(nmpc_batch* b, void** table, size_t* bytes)
 {
     if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (table) *table = b->sb_on ? b->sbounds : nullptr;
-    if (bytes) *bytes = b->sb_on ? sb_bytes(b) : 0;
+    if (table) *table = b->sbounds.view();
+    if (bytes) *bytes = b->sbounds.on ? sizeof(float) * b->sbounds.floats : 0;
     return NMPC_OK;
 }
 
-int nmpc_batch_clear_stage_bounds(nmpc_batch* b)
-{
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    b->sb_on = false;  // (the allocation stays for the next writer, which refills it)
-    return NMPC_OK;
-}
+int nmpc_batch_clear_stage_bounds(nmpc_batch* b) { return table_clear(b, &nmpc_batch::sbounds); }
 
 int nmpc_batch_set_robot_model(nmpc_batch* b, int B, const float* p, const unsigned char* mask, void* stream)
 {
-    // the checks that need no handle come first
-    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
-    if (!p) return set_err(NMPC_ERR_ARG, "robot model: p is NULL");
-    if (const int rc = check_batch(b, B)) return rc;
-    if (B == 0) return NMPC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (const int rc = rm_table(b, s)) return rc;
-    return hip_err(launch_rm_set(b->rmodel, b->capacity, B, b->np, p, mask, s), "robot_model launch");
+    return table_write(b, B, p ? nullptr : "robot model: p is NULL", rm_table, stream, "robot_model launch",
+                       [&](hipStream_t s) {
+                           const int off[2] = {0, b->np};  // the one field p
+                           const float* const fields[1] = {p};
+                           return launch_rows_set<1>(b->rmodel.p, b->capacity, B, off, fields, mask, s);
+                       });
 }
 
 int nmpc_batch_robot_model(nmpc_batch* b, float** table, int* rows, int* stride)
 {
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    if (table) *table = b->rm_on ? b->rmodel : nullptr;
-    if (rows) *rows = b->np;
-    if (stride) *stride = b->capacity;
-    return NMPC_OK;
+    return rows_view(b, &nmpc_batch::rmodel, table, rows, stride);
 }
 
-int nmpc_batch_clear_robot_model(nmpc_batch* b)
-{
-    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
-    b->rm_on = false;  // (the allocation stays for the next writer, which refills it)
-    return NMPC_OK;
-}
+int nmpc_batch_clear_robot_model(nmpc_batch* b) { return table_clear(b, &nmpc_batch::rmodel); }
 
 int nmpc_batch_set_record_layout(nmpc_batch* b, int layout)
 {
@@ -1196,8 +1180,7 @@ int fleet_sim(nmpc_batch* b, int B, float* path, float* s, float* pose, float* v
     if (!path || !s || !pose || !vel || !traj || (advance && !u0)) return set_err(NMPC_ERR_ARG, "NULL argument");
     const hipError_t e = with_model(b->prm.model, [&](auto m) {
         return launch_fleet_sim<decltype(m)>(b->kp, B, b->capacity, path, s, pose, vel, steer, u0, status, b->carried,
-                                             traj, traj_len, advance, renew, b->rm_on ? b->rmodel : nullptr,
-                                             (hipStream_t)stream);
+                                             traj, traj_len, advance, renew, b->rmodel.view(), (hipStream_t)stream);
     });
     return hip_err(e, "fleet_sim launch");
 }

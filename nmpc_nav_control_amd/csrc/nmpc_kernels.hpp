@@ -92,16 +92,16 @@ struct KArgs {
     float* stage_out_h;
     const float* stage_out_d;
     int stage_out_n;
-    // per-robot bounds and weights (robot_params.hip): the handle's table [rows][sstride], rows as rp_rows() of the
+    // per-robot bounds and weights (robot_tables.hip): the handle's table [rows][sstride], rows as rp_rows() of the
     // model lays them out; nullptr: the table is off and every robot takes KParams' values. (The row offsets are
     // compile-time values of the model in the kernels, not launch arguments: the team kernel has no scalar registers
     // to spare.)
     const float* rparams;
-    // stage-varying bounds (stage_bounds.hip): the handle's stage table, every robot's box at every stage of the
+    // stage-varying bounds (robot_tables.hip): the handle's stage table, every robot's box at every stage of the
     // horizon (sb_at below); nullptr: the table is off and a robot's box is the same at every stage (rparams, else
     // KParams). While it is on, the bound rows of rparams and of KParams reach no launch
     const float* sbounds;
-    // per-robot model parameters (robot_model.hip): the handle's model table [NP][sstride]; nullptr: the table is off
+    // per-robot model parameters (robot_tables.hip): the handle's model table [NP][sstride]; nullptr: the table is off
     // and every robot takes KParams::p. While it is on, KParams::p reaches no launch (robot_vals, sqp_steps.hpp)
     const float* rmodel;
 };
@@ -120,7 +120,7 @@ __host__ __device__ constexpr RpRows rp_rows(int nx, int nu, int nbx, int nbu)
     return r;
 }
 constexpr int kRpRowsMax = 48;  // omni4: 4 * 4 + 15 + 11 = 42
-// one robot's column of the table (the handle's own parameters: launch_rp_fill's kernel argument)
+// one robot's column of a table (the handle's own values: the fill kernels' argument)
 struct RpColumn {
     float v[kRpRowsMax];
 };
@@ -168,27 +168,23 @@ hipError_t launch_node_order(const int* key, const unsigned char* active, int B,
 hipError_t launch_init_iterate(float* xbar, float* ubar, float* carried, unsigned char* warm, int B, int stride, int N,
                                int nx, int nu, int nbx, int mode, hipStream_t stream);
 hipError_t launch_forget_warm(unsigned char* warm, const unsigned char* mask, int B, hipStream_t stream);
-// the per-robot table's writers (robot_params.hip), each one launch: every robot's column = col (the first `cap`
-// robots); the rows of the non-NULL fields of rp ([n][B] each) for the robots with mask[i] != 0 (nullptr: all); and
-// the batched nmpc_model_params_set_limits (each array [B] or nullptr: those rows stay)
-hipError_t launch_rp_fill(float* table, int cap, int rows, const RpColumn& col, hipStream_t stream);
-hipError_t launch_rp_set(float* table, int cap, int B, const RpRows& rr, const nmpc_robot_params& rp,
-                         const unsigned char* mask, hipStream_t stream);
+// The writers of the three per-robot device tables (robot_tables.hip), each one launch; mask: the robots with
+// mask[i] != 0 (nullptr: all of the first B).
+// Row-major tables [rows][cap] (the per-robot table, the model table): fill: every robot's column = col (the first
+// `cap` robots); set: the rows of the non-NULL fields of a list of kFields fields (field f: the rows [off[f],
+// off[f + 1]), its source src[f] [n][B]; kRpFields fields for the per-robot table, the one field p for the model
+// table); rp_limits: the batched nmpc_model_params_set_limits (each array [B] or nullptr: those rows stay)
+hipError_t launch_rows_fill(float* table, int cap, int rows, const RpColumn& col, hipStream_t stream);
+template <int kFields>
+hipError_t launch_rows_set(float* table, int cap, int B, const int (&off)[kFields + 1],
+                           const float* const (&src)[kFields], const unsigned char* mask, hipStream_t stream);
 hipError_t launch_rp_limits(float* table, int cap, int B, const RpRows& rr, int tric, const float* v_max,
                             const float* a_max, const float* alpha_min, const float* alpha_max,
                             const float* dalpha_max, const unsigned char* mask, hipStream_t stream);
-// the model table's writers (robot_model.hip), each one launch: every robot's column = p (the first `cap` robots); and
-// the np rows of src ([np][B]) for the robots with mask[i] != 0 (nullptr: all)
-struct RmColumn {
-    float v[3];
-};
-hipError_t launch_rm_fill(float* table, int cap, int np, const RmColumn& p, hipStream_t stream);
-hipError_t launch_rm_set(float* table, int cap, int B, int np, const float* src, const unsigned char* mask,
-                         hipStream_t stream);
-// the stage table's writers (stage_bounds.hip), each one launch. sb: the table, N + 1 stages of `cap` robots.
-// fill: every stage of every robot = the robot's column of the per-robot table rp (rows rr, stride cap) when rp is
-// not nullptr, else col's first sb_rows values (lbx ubx lbu ubu of the handle). set: the non-NULL fields of s for the
-// robots with mask[i] != 0. limits: the per-stage nmpc_model_params_set_limits. shift: stage k = stage min(k + n, last)
+// The stage table sb, N + 1 stages of `cap` robots. fill: every stage of every robot = the robot's column of the
+// per-robot table rp (rows rr, stride cap) when rp is not nullptr, else col's first sb_rows values (lbx ubx lbu ubu of
+// the handle). set: the non-NULL fields of s. limits: the per-stage nmpc_model_params_set_limits. shift: stage k =
+// stage min(k + n, last)
 struct SbDims {
     int N, cap, nbx, nbu;
 };

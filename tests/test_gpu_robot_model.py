@@ -1,4 +1,4 @@
-"""GPU tests of the model table (csrc/robot_model.hip, robot_vals in csrc/sqp_steps.hpp, the team kernel's MT
+"""GPU tests of the model table (csrc/robot_tables.hip, robot_vals in csrc/sqp_steps.hpp, the team kernel's MT
 instantiations) against one fp64 Oracle per robot (tests/robot_model_cases.py).
 
 Tolerance of the oracle comparisons: test_gpu_parity.py's, |u0 - u0_oracle|_inf and |cmd - cmd_oracle|_inf <= 1e-3 with
@@ -30,7 +30,7 @@ from tests.path_cases import random_paths
 from tests.test_gpu_node import N as NODE_N
 from tests.test_gpu_node import Tick, mixed_fleet
 from tests.test_gpu_node import params as node_params
-from tests.test_gpu_robot_params import CASES, FORMS, MODELS, TOL_U, Loop, check_tick, make_solver, state_of, t, table_args
+from tests.table_harness import CASES, FORMS, MODELS, TOL_U, Loop, check_tick, make_solver, state_of, t, table_args
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")

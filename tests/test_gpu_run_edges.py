@@ -11,7 +11,7 @@ the hack's boundary, +-pi crossings once and many times per list, a goal across 
 
 Matrix: model x form x N in {20, 21, 22} (N + 1 meets every remainder of the row-parallel kernel's three-buffer
 rotation and of the team pass's two-ahead loads), and N in {1, 2} on the plain team form and the default form. The
-forms are tests/test_gpu_robot_params.py's and the two-wave segmented row-parallel form (>= 257 robots; omni4 takes
+forms are tests/table_harness.py's and the two-wave segmented row-parallel form (>= 257 robots; omni4 takes
 the team kernel there, so it has none). Placement: rc.placements -- B = 81 (257), no multiple of 4, each of the
 traj_len = N and the multi-crossing cases once in slot 0 and in the last slot (one batch per such case) and on both
 sides of a 16-robot boundary.
@@ -47,7 +47,7 @@ from nmpc_nav_control_amd._lib import default_params
 from nmpc_nav_control_amd.batch import BatchSolver
 from oracle.oracle import Oracle
 from tests.test_gpu_parity import TOL_U, TOL_UTRAJ, TOL_X
-from tests.test_gpu_robot_params import FORMS as PARAM_FORMS
+from tests.table_harness import FORMS as PARAM_FORMS
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")

@@ -1,4 +1,4 @@
-"""GPU tests of the stage table (csrc/stage_bounds.hip, stage_box in csrc/sqp_steps.hpp) against one fp64 solve per
+"""GPU tests of the stage table (csrc/robot_tables.hip, stage_box in csrc/sqp_steps.hpp) against one fp64 solve per
 robot on the QP with the profile's bounds spliced in (tests/stage_bound_cases.py).
 
 Tolerance of the oracle comparisons: test_gpu_parity.py's, |u0 - u0_oracle|_inf and |cmd - cmd_oracle|_inf <= 1e-3 with
@@ -22,7 +22,7 @@ from tests.test_gpu_node import N as NODE_N
 from tests.test_gpu_node import Tick, mixed_fleet
 from tests.test_gpu_node import params as node_params
 from tests.test_gpu_queue import QTick
-from tests.test_gpu_robot_params import CASES, FORMS, MODELS, TOL_U, Loop, make_solver, state_of, t, table_args
+from tests.table_harness import CASES, FORMS, MODELS, TOL_U, Loop, make_solver, state_of, t, table_args
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
