@@ -139,7 +139,11 @@ int nmpc_batch_solve_iterate(nmpc_batch* b, int B, const float* x0, const float*
  * The unwrap decision (|delta| > pi) and the terminal-weight hack's equality test are taken in fp32 on the fp32
  * inputs. A heading step within one fp32 ulp of pi may therefore unwrap the other way than the fp64 reference would
  * (e.g. from pose theta = 0 to a reference theta = (float)pi), and two references that differ by less than an fp32
- * ulp at magnitude 2 pi may compare equal after the unwrap; both outcomes are valid headings. */
+ * ulp at magnitude 2 pi may compare equal after the unwrap; both outcomes are valid headings.
+ * x and y are absolute fp32 map coordinates throughout: the 1e-3 parity with the fp64 reference is measured up to
+ * 64 m from the map origin; beyond that the first solve of a robot and every solve after a reset lose accuracy in
+ * proportion to the distance (u0 within 1e-2 at 4096 m, status 0 throughout), warm solves do not (DESIGN.md
+ * "Coordinate range"). */
 int nmpc_batch_run(nmpc_batch* b, int B, const float* pose, const float* vel, const float* steer,
                    const float* traj, const int* traj_len, const unsigned char* reset, float* cmd, float* u0,
                    int* status, int* qp_iter, float* qp_res, void* stream);

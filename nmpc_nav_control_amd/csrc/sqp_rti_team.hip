@@ -489,10 +489,10 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                 load_p0(k + 2, rw[(i + 2) % 3]);  // two stages ahead (clamped)
                 const Row& c = rw[i];
                 const Row& n1 = rw[(i + 1) % 3];
-                float xn[NX], g[NX];
+                float dxn[NX], g[NX];
 #pragma unroll
-                for (int q = 0; q < NX; q++) { xn[q] = 0.0f; g[q] = 0.0f; }
-                if (k < N) rk4_column<M>(c.xb, c.ub, P, mp, lv ? r : NU, xn, g);
+                for (int q = 0; q < NX; q++) { dxn[q] = 0.0f; g[q] = 0.0f; }
+                if (k < N) rk4_column<M>(c.xb, c.ub, P, mp, lv ? r : NU, dxn, g);
                 float zbar = 0.0f;
 #pragma unroll
                 for (int j = 0; j < NU; j++)
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
                 float bk = 0.0f;
 #pragma unroll
                 for (int q = 0; q < NX; q++)
-                    if (xi == q) bk = xn[q] - n1.xb[q];
+                    if (xi == q) bk = (c.xb[q] - n1.xb[q]) + dxn[q];  // (p0_stage_inputs' order)
                 p0_body(k, zbar, c.yr, c.tr, c.lp, g, bk, RP ? c.bx : make_float2(lo_b, hi_b));
                 if (k == N) stop = true;
             });

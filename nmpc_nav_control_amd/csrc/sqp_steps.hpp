@@ -213,8 +213,8 @@ __device__ __forceinline__ void const_rows(const KParams& P, const typename M::P
                                            float (&grow)[M::NX + M::NU])
 {
     constexpr int NX = M::NX, NU = M::NU, NV = NX + NU, NGV = M::NGV;
-    float xn0[NX], g0[NX];
-    rk4_column<M>(xb, ub, P, mp, c.lv ? r : NU, xn0, g0);
+    float dxn0[NX], g0[NX];
+    rk4_column<M>(xb, ub, P, mp, c.lv ? r : NU, dxn0, g0);
 #pragma unroll
     for (int i = 0; i < NX; i++) gcol[i] = (c.lv && i >= NGV) ? g0[i] : 0.0f;
     sfor<0, NV>([&](auto vc) {
@@ -259,7 +259,7 @@ template <class M>
 struct StageLds {
     static constexpr int SF = 5 + M::NGV;
     static constexpr int ZBAR = 0, YREF = 16, LL = 32, LU = 48, DEFECT = 64;  // iterate entry, yref entry (solve
-    // mode), warm multipliers, defect b_k = xn_i - xbar_{k+1,i}
+    // mode), warm multipliers, defect b_k = (xbar_{k,i} - xbar_{k+1,i}) + dxn_i
     static constexpr int gv(int i) { return (5 + i) * 16; }                   // the NGV varying Jacobian rows
     __device__ static size_t at(int k, int r) { return (size_t)k * SF * 16 + r; }
 };
@@ -277,15 +277,17 @@ __device__ __forceinline__ P0In<M> p0_stage_inputs(const KParams& P, const typen
 {
     constexpr int NX = M::NX, NU = M::NU;
     P0In<M> o;
-    float xn[NX];
+    float dxn[NX];
 #pragma unroll
-    for (int i = 0; i < NX; i++) { xn[i] = 0.0f; o.g[i] = 0.0f; }
+    for (int i = 0; i < NX; i++) { dxn[i] = 0.0f; o.g[i] = 0.0f; }
     o.bk = 0.0f;
     if (k < N) {
-        rk4_column<M>(x, u, P, mp, c.lv ? r : NU, xn, o.g);
+        rk4_column<M>(x, u, P, mp, c.lv ? r : NU, dxn, o.g);
+        // (x - xnext first: both are stored iterate entries a stage apart, so the difference is exact at any
+        // distance from the map origin, and only then the step's increment)
 #pragma unroll
         for (int i = 0; i < NX; i++)
-            if (c.is_x && c.xi == i) o.bk = xn[i] - xnext;
+            if (c.is_x && c.xi == i) o.bk = (x[i] - xnext) + dxn[i];
     }
     o.zb = 0.0f;
 #pragma unroll

@@ -371,10 +371,13 @@ __device__ __forceinline__ int xcomp(int xi)
 }
 
 // Column `col` (slot convention: col < NU input col, else state col - NU) of the RK4 map's sensitivity at
-// (x, u), propagated by one lane through the four stages, together with the nominal step xn.
+// (x, u), propagated by one lane through the four stages, together with the nominal step's increment
+// dxn = xn - x. The increment and not xn: x and y are absolute map coordinates, and xn = x + dxn would round a step of
+// ~1e-2 m at ulp(|x|) before the shooting defect subtracts the next stage's state; the callers form
+// b_k = (x - x_next) + dxn, whose first term is exact (DESIGN.md "Coordinate range").
 template <class M>
 __device__ __forceinline__ void rk4_column(const float* x, const float* u, const KParams& P,
-                                           const typename M::Par& mp, int col, float* xn, float* g)
+                                           const typename M::Par& mp, int col, float* dxn, float* g)
 {
     constexpr int NX = M::NX, NU = M::NU;
     const float h = P.dt;
@@ -416,7 +419,7 @@ __device__ __forceinline__ void rk4_column(const float* x, const float* u, const
     const float h6 = h * (1.0f / 6.0f);
 #pragma unroll
     for (int i = 0; i < NX; i++) {
-        xn[i] = x[i] + h6 * acc[i];
+        dxn[i] = h6 * acc[i];
         g[i] = s0[i] + h6 * dacc[i];
     }
 }

@@ -5,12 +5,18 @@ from nmpc_nav_control_amd.scenario import make_fleet, refs_for
 from oracle.oracle import Oracle
 
 
-def oracle_closed_loop(model, N, B, ticks, seed=20250824, o=None, start=0, u0_log=None):
+def oracle_closed_loop(model, N, B, ticks, seed=20250824, o=None, start=0, u0_log=None, fl=None, quant=None,
+                       reset_at=None, log=None):
     """Run the fp64 oracle in closed loop (plant = RK4 of the model) for `ticks` ticks over robots
     [start, start + B) of the seeded fleet. Returns the oracle and, for the last tick, the solve inputs
-    (x0, yref, We, xbar, ubar) per robot; appends each tick's u0 [B][nu] to `u0_log` when given."""
+    (x0, yref, We, xbar, ubar) per robot; appends each tick's u0 [B][nu] to `u0_log` when given.
+
+    fl: that fleet instead (a make_fleet dict of B robots, e.g. a shifted one). quant(tick, pose [3], traj [n][3]) ->
+    (pose, traj): what the solver is given in place of the plant's fp64 pose and references (e.g. both rounded to
+    fp32). reset_at: {tick: robots whose iterate is zeroed before that tick's solve}. log: a list that gets one dict
+    per tick, status / qp_iter [B] and u0 [B][nu]."""
     o = o or Oracle(model, N, rule="batched")
-    fl = make_fleet(model, B, seed=seed, start=start)
+    fl = make_fleet(model, B, seed=seed, start=start) if fl is None else fl
     pose = fl["pose"].T.astype(np.float64).copy()
     vel = fl["vel"].T.astype(np.float64).copy()
     steer = fl["steer"].astype(np.float64).copy()
@@ -24,11 +30,18 @@ def oracle_closed_loop(model, N, B, ticks, seed=20250824, o=None, start=0, u0_lo
     for t in range(ticks):
         rec = []
         u0s = np.full((B, o.nu), np.nan)
+        sts, its = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        if log is not None:
+            log.append(dict(status=sts, qp_iter=its, u0=u0s))
+        for i in (reset_at or {}).get(t, ()):
+            xbar[i], ubar[i] = 0.0, 0.0
         for i in range(B):
             traj, s[i] = refs_for(fl["path"], i, pose[i], s[i], N, o.prm.dt_ctrl)
-            x0, yref, We = o.prepare(pose[i], vel[i], steer[i], traj, carried[i])
+            given = (pose[i], traj) if quant is None else quant(t, pose[i], traj)
+            x0, yref, We = o.prepare(given[0], vel[i], steer[i], given[1], carried[i])
             rec.append((x0, yref, We, xbar[i].copy(), ubar[i].copy()))
-            st, _, xb, ub = o.sqp_rti(xbar[i], ubar[i], x0, yref, We)
+            st, stats, xb, ub = o.sqp_rti(xbar[i], ubar[i], x0, yref, We)
+            sts[i], its[i] = st, stats["qp_iter"]
             if st != 0:
                 continue
             xbar[i], ubar[i] = xb, ub

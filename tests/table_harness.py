@@ -10,6 +10,7 @@ import torch
 from nmpc_nav_control_amd._lib import default_params
 from nmpc_nav_control_amd.batch import BatchSolver
 from nmpc_nav_control_amd.scenario import make_fleet
+from tests import far_field_cases as ff
 from tests import robot_param_cases as rc
 
 TOL_U = 1e-3
@@ -33,12 +34,13 @@ def state_of(s):
 
 class Loop:
     """test_run_closed_loop_matches_oracle's loop on the harness plant: device inputs and outputs of B robots of the
-    seeded fleet, one run() per tick, the host copies of the tick's inputs for the oracles."""
+    seeded fleet, one run() per tick, the host copies of the tick's inputs for the oracles. offset: the fleet moved
+    from the map origin (tests/far_field_cases.py:shift_fleet; [2], or [B][2] for one offset per robot)."""
 
-    def __init__(self, solver, model, B, seed=rc.SEED):
+    def __init__(self, solver, model, B, seed=rc.SEED, offset=(0.0, 0.0)):
         self.s, self.model, self.B = solver, model, B
         N = solver.N
-        fl = self.fl = make_fleet(model, B, seed=seed)
+        fl = self.fl = ff.shift_fleet(make_fleet(model, B, seed=seed), offset)
         solver.state()[2].copy_from(_pad(t(fl["carried"]), solver.capacity))
         self.pose, self.vel, self.steer = t(fl["pose"]), t(fl["vel"]), t(fl["steer"])
         self.path, self.prog = t(fl["path"]), t(fl["s"])
@@ -58,8 +60,8 @@ class Loop:
                 f64(self.steer.cpu().numpy()) if self.model == "tric" else None,
                 f64(self.traj.cpu().numpy().transpose(2, 0, 1)), np.ascontiguousarray(self.tlen.cpu().numpy(), np.int32))
 
-    def run(self):
-        self.s.run(self.pose, self.vel, self.traj, steer=self.steer_arg, traj_len=self.tlen, **self.out)
+    def run(self, reset=None):
+        self.s.run(self.pose, self.vel, self.traj, steer=self.steer_arg, traj_len=self.tlen, reset=reset, **self.out)
         torch.cuda.synchronize()
 
     def advance(self):
@@ -76,9 +78,10 @@ def _pad(a, cap):
     return out
 
 
-def check_tick(loop, fleet, inp, tick):
-    """one tick's u0 / cmd / status against the per-robot oracles on the same inputs"""
-    cmd_o, u0_o, st_o, it_o = fleet.tick(*inp)
+def check_tick(loop, fleet, inp, tick, tol=TOL_U, **kw):
+    """one tick's u0 / cmd / status against the per-robot oracles on the same inputs (kw: further arguments of the
+    oracles' tick); returns the two errors"""
+    cmd_o, u0_o, st_o, it_o = fleet.tick(*inp, **kw)
     st = loop.out["status"].cpu().numpy()
     eu = np.abs(loop.out["u0"].cpu().numpy().T - u0_o).max()
     ec = np.abs(loop.out["cmd"].cpu().numpy().T - cmd_o).max()
@@ -86,8 +89,9 @@ def check_tick(loop, fleet, inp, tick):
           f"{loop.out['qp_iter'].cpu().numpy().tolist()}; |du0| {eu:.2e} |dcmd| {ec:.2e}")
     assert (st_o == 0).all(), (tick, st_o)
     assert (st == 0).all(), (tick, st)
-    assert eu <= TOL_U, (tick, eu)
-    assert ec <= TOL_U, (tick, ec)
+    assert eu <= tol, (tick, eu)
+    assert ec <= tol, (tick, ec)
+    return eu, ec
 
 
 # The launch forms: (environment, qp_ipm, what nmpc_batch_plan_ex must report). NMPC_AMD_REC_SPLIT selects the team

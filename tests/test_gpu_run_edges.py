@@ -116,7 +116,13 @@ def state_host(s, B, o):
 
 @pytest.mark.parametrize("model,form,N", MATRIX)
 def test_run_edges_match_oracle(built, monkeypatch, model, form, N):
-    cs = rc.cases(model, N)
+    check_edges(monkeypatch, model, form, N, rc.cases(model, N))
+
+
+def check_edges(monkeypatch, model, form, N, cs, scale=1.0):
+    """the table cs (rc.cases(model, N), or that table moved: tests/test_gpu_far_field.py) through nmpc_batch_run in
+    every placement, each tick replayed through the oracle; scale: the factor on the three tolerances. Returns the
+    maxima."""
     o = Oracle(model, N, rule="batched")
     worst = dict(u0=0.0, cmd=0.0, carried=0.0, x=0.0, u=0.0)
     for order in rc.placements(cs, FORMS[form][3]):
@@ -145,9 +151,10 @@ def test_run_edges_match_oracle(built, monkeypatch, model, form, N):
             assert (st_o == 0).all(), (tick, [(names[i], int(st_o[i])) for i in np.flatnonzero(st_o)])
             assert (st == 0).all(), (tick, [(names[i], i, int(st[i])) for i in np.flatnonzero(st)])
             for k, tol in (("u0", TOL_U), ("cmd", TOL_U), ("carried", TOL_U), ("x", TOL_X), ("u", TOL_UTRAJ)):
-                assert err[k].max() <= tol, (tick, k, float(err[k].max()), where[k])
+                assert err[k].max() <= scale * tol, (tick, k, float(err[k].max()), where[k])
         s.close()
     print(f"maxima {model} {form} N={N}: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    return worst
 
 
 def run_ticks(s, model, cs, order, variant):
