@@ -143,7 +143,8 @@ int nmpc_batch_solve_iterate(nmpc_batch* b, int B, const float* x0, const float*
  * x and y are absolute fp32 map coordinates throughout: the 1e-3 parity with the fp64 reference is measured up to
  * 64 m from the map origin; beyond that the first solve of a robot and every solve after a reset lose accuracy in
  * proportion to the distance (u0 within 1e-2 at 4096 m, status 0 throughout), warm solves do not (DESIGN.md
- * "Coordinate range"). */
+ * "Coordinate range"). A per-robot map frame (nmpc_batch_set_robot_frame below) removes the limit: the fp32 positions
+ * are then relative to an origin near the robot and the 1e-3 parity holds at any distance from the map origin. */
 int nmpc_batch_run(nmpc_batch* b, int B, const float* pose, const float* vel, const float* steer,
                    const float* traj, const int* traj_len, const unsigned char* reset, float* cmd, float* u0,
                    int* status, int* qp_iter, float* qp_res, void* stream);
@@ -528,6 +529,71 @@ int nmpc_batch_robot_model(nmpc_batch* b, float** table, int* rows, int* stride)
 /* Turn the model table off: launches use the handle's p again. The next writer call starts a fresh table from the
  * handle's p. (Host-side switch: it applies to the launches enqueued after it.) */
 int nmpc_batch_clear_robot_model(nmpc_batch* b);
+
+/* Per-robot map frames. x and y are fp32 from the inputs to the stored iterate, so in absolute map coordinates the
+ * 1e-3 parity holds up to 64 m from the map origin only (nmpc_batch_run above), and at 4.6e6 m, a projected map
+ * coordinate, an fp32 position has an ulp of half a metre. The SQP-RTI step is translation-covariant in exact
+ * arithmetic: no model's f reads x or y, the position rows of the stage Jacobian are the identity and no bound touches
+ * x or y, so a solve whose iterate, x0 and references are all relative to a point near the robot is the solve the
+ * reference does, at fp32's full resolution. The handle therefore owns a fourth device table, the frame
+ * table: [2][capacity], fp64, instance-minor, row 0 every robot's origin x and row 1 its origin y, in map coordinates;
+ * 16 bytes per robot. It is allocated by the first nmpc_batch_set_robot_frame or nmpc_batch_recentre call and starts
+ * with the origin (0, 0) in every column.
+ * Rules:
+ *   - While the table is on, every fp32 position of every launch of the handle is in robot i's frame, map coordinate
+ *     minus origin i: as inputs pose x and y, traj x and y, goal x and y, solve mode's x0 rows 0 and 1 and yref
+ *     components 0 and 1; as outputs x1, xtraj and traj_out; and the resident iterate's position rows
+ *     (nmpc_batch_state). Headings, velocities, the carried refs, u0, cmd, the multipliers and the other three tables
+ *     are unaffected.
+ *   - Every fp64 path quantity stays in map coordinates: the nmpc_path_segment coefficients, near, and the path
+ *     parameter. The launches that read segments -- nmpc_batch_run_path, _follow_path and both node ticks -- bridge
+ *     the two in fp64: the nearest-point search and the path errors take the robot at (double)pose + origin, the
+ *     end-of-trajectory test compares that map position with the fp64 last pose, and every reference pose the march
+ *     emits becomes (float)(p - origin), for the solve and for traj_out: one fp64 subtraction, then the one rounding
+ *     it had. GoToPose compares goal and pose, both in the frame, as before.
+ *   - nmpc_batch_run, _solve and _solve_iterate read nothing new: their inputs are frame values by contract. A reset
+ *     (reset[i] = 1) or nmpc_batch_init_iterate puts the iterate at the frame origin, which is the point: the first
+ *     solve's primal step is then the robot's distance from its origin, not from the map's. This departs from the
+ *     reference, whose {name}_acados_create / _reset leave the iterate at the map origin, as qp_warm_start departs
+ *     from its cold IPM start; by the covariance above it is the solve the reference would do in exact arithmetic.
+ *   - While it is off (never written, or after nmpc_batch_clear_robot_frame) every launch computes exactly what it
+ *     computed without this interface, bit for bit.
+ *   - The four tables are independent: any combination of them being on or off is legal.
+ *   - Each writer is one small launch on `stream`, with no host synchronisation and no host-side validation (a NaN
+ *     origin gives that robot NaN positions and fails it alone, with status 1, as a NaN input does).
+ *   - Placing a robot somewhere new: set its frame, then reset it (reset[i] = 1) or nmpc_batch_init_iterate.
+ *   - Out of scope: the capsule ABI (its iterate travels with the caller and keeps map coordinates);
+ *     nmpc_batch_solve_iterate's caller-held iterate (nmpc_batch_set_robot_frame moves the resident one only); the
+ *     harness plant (nmpc_fleet_sim_step* works on whatever fp32 positions it is given, under a frame those are frame
+ *     values, and it does not follow a changing origin); rotated frames. nmpc_path_nearest and nmpc_path_discretize
+ *     take no handle and stay in map coordinates.
+ * Argument errors (NMPC_ERR_ARG): B out of range, a NULL payload (origin, pose_map, map / in / out), n < 0, c < 2, a
+ * NULL handle. radius is not an argument error: a NaN or +inf radius moves nothing. */
+/* Write the origins of robots [0, B) where mask[i] != 0 (mask [B] device, NULL: all) from origin [2][B] (device, fp64),
+ * and in the same launch move those robots' resident iterate so that its map position does not change: the x and y
+ * row of every stage becomes (float)((double)x + (o_old - o_new)). Nothing else of the robot changes: warm flag,
+ * scratch records, carried refs, ubar, the other rows of xbar, the placement key. */
+int nmpc_batch_set_robot_frame(nmpc_batch* b, int B, const double* origin, const unsigned char* mask, void* stream);
+/* The same launch with a computed origin, which keeps a long-running robot near its origin without a host decision:
+ * pose_map [2 or 3][B] (device, fp64; rows 0 and 1 are read) is every robot's map position. A masked robot with
+ * max(|x_map - o_x|, |y_map - o_y|) > radius gets the origin (rint(x_map), rint(y_map)), whole metres, its iterate
+ * moves as above and moved[i] = 1; every other robot gets moved[i] = 0 and is untouched (moved [B] device, or NULL). A
+ * non-finite position, or a NaN radius, moves nothing. */
+int nmpc_batch_recentre(nmpc_batch* b, int B, const double* pose_map, double radius, const unsigned char* mask,
+                        unsigned char* moved, void* stream);
+/* Map coordinates into the robots' frames and back, for arrays [n][c][B] (device): components 0 and 1 of each group of
+ * c become (float)(v - origin) / (double)v + origin, the others are only converted. (n, c) = (1, 3) for pose and goal,
+ * (N+1, 3) for traj and traj_out, (1, NX) for x0 and x1, (N+1, ny_in) for yref, (N+1, NX) for xtraj. While the table
+ * is off the origin is (0, 0). */
+int nmpc_batch_to_frame(nmpc_batch* b, int B, const double* map, int n, int c, float* out, void* stream);
+int nmpc_batch_from_frame(nmpc_batch* b, int B, const float* in, int n, int c, double* map, void* stream);
+/* The table's device view for checkpoints: *table [2][stride] fp64 (stride = capacity), or NULL while the table is
+ * off. Each output may be NULL. Restore it before the iterate, which is relative to it. */
+int nmpc_batch_robot_frame(nmpc_batch* b, double** table, int* stride);
+/* Move every robot's iterate back to map coordinates (the writer with origin 0 for the whole capacity, one launch on
+ * `stream`), then turn the table off: the launches enqueued after it take every position as a map coordinate again.
+ * The next writer call starts a fresh table of zero origins. */
+int nmpc_batch_clear_robot_frame(nmpc_batch* b, void* stream);
 
 /* Record layout of the team kernel's single-direction scratch records, a per-handle choice fixed at create time
  * and changed only by this call (never by other handles):

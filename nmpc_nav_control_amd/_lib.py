@@ -122,6 +122,8 @@ BATCH_SYMBOLS = [
     "nmpc_batch_set_stage_bounds", "nmpc_batch_set_stage_limits", "nmpc_batch_shift_stage_bounds",
     "nmpc_batch_stage_bounds", "nmpc_batch_clear_stage_bounds",
     "nmpc_batch_set_robot_model", "nmpc_batch_robot_model", "nmpc_batch_clear_robot_model",
+    "nmpc_batch_set_robot_frame", "nmpc_batch_recentre", "nmpc_batch_to_frame", "nmpc_batch_from_frame",
+    "nmpc_batch_robot_frame", "nmpc_batch_clear_robot_frame",
     "nmpc_fleet_sim_step", "nmpc_fleet_sim_step_renew", "nmpc_fleet_hash",
     "nmpc_last_error", "nmpc_version", "nmpc_path_discretize", "nmpc_path_nearest", "nmpc_codegen_default", "nmpc_capsule_new",
     "nmpc_capsule_delete", "nmpc_capsule_create", "nmpc_capsule_reset", "nmpc_capsule_update_params",
@@ -202,6 +204,12 @@ def lib():
     L.nmpc_batch_set_robot_model.argtypes = [vp, i, vp, vp, vp]
     L.nmpc_batch_robot_model.argtypes = [vp, ctypes.POINTER(vp), c_int_p, c_int_p]
     L.nmpc_batch_clear_robot_model.argtypes = [vp]
+    L.nmpc_batch_set_robot_frame.argtypes = [vp, i, vp, vp, vp]
+    L.nmpc_batch_recentre.argtypes = [vp, i, vp, ctypes.c_double, vp, vp, vp]
+    L.nmpc_batch_to_frame.argtypes = [vp, i, vp, i, i, vp, vp]
+    L.nmpc_batch_from_frame.argtypes = [vp, i, vp, i, i, vp, vp]
+    L.nmpc_batch_robot_frame.argtypes = [vp, ctypes.POINTER(vp), c_int_p]
+    L.nmpc_batch_clear_robot_frame.argtypes = [vp, vp]
     L.nmpc_fleet_sim_step.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     L.nmpc_fleet_sim_step_renew.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(FleetRenew), vp]
     L.nmpc_fleet_hash.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint]

@@ -29,7 +29,7 @@ def _ptr(t, dtype=None, shape=None, name="argument"):
     return ctypes.c_void_p(t.data_ptr())
 
 
-F32, I32, I64, U8 = torch.float32, torch.int32, torch.int64, (torch.uint8, torch.bool)
+F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, (torch.uint8, torch.bool)
 
 
 def _stream(stream):
@@ -271,10 +271,68 @@ class BatchSolver:
         """Turn the model table off: launches use the handle's p again."""
         check(lib().nmpc_batch_clear_robot_model(self._h), "nmpc_batch_clear_robot_model")
 
+    def set_robot_frame(self, origin, mask=None, stream=None):
+        """Per-robot map frames (nmpc_batch_set_robot_frame): origin a float64 device tensor [2][B], every robot's
+        origin x and y in map coordinates; mask uint8 [B] selects the robots (None: all). One launch on the stream,
+        which also moves those robots' resident iterate so that its map position stays. From then on every fp32
+        position of this solver's launches is relative to the robot's origin, and the float64 path segments stay in
+        map coordinates (until clear_robot_frame)."""
+        B = self._batch_of(origin)
+        check(lib().nmpc_batch_set_robot_frame(self._h, B, _ptr(origin, F64, (2, B), "origin"),
+                                               _ptr(mask, U8, (B,), "mask"), _stream(stream)),
+              "nmpc_batch_set_robot_frame")
+
+    def recentre(self, pose_map, radius, mask=None, moved=None, stream=None):
+        """set_robot_frame with a computed origin (nmpc_batch_recentre): pose_map float64 [2 or 3][B], the robots' map
+        positions. A masked robot farther than radius (in x or y) from its origin gets the origin rint(position) and
+        moved[i] = 1 (moved uint8 [B], optional); the others stay, moved[i] = 0."""
+        B = self._batch_of(pose_map)
+        if pose_map.shape[0] not in (2, 3):
+            raise ValueError(f"pose_map: expected 2 or 3 rows, got {pose_map.shape[0]}")
+        check(lib().nmpc_batch_recentre(self._h, B, _ptr(pose_map, F64, None, "pose_map"), float(radius),
+                                        _ptr(mask, U8, (B,), "mask"), _ptr(moved, torch.uint8, (B,), "moved"),
+                                        _stream(stream)), "nmpc_batch_recentre")
+
+    def to_frame(self, map_values, out=None, stream=None):
+        """Map coordinates into the robots' frames (nmpc_batch_to_frame): map_values float64 [n][c][B] or [c][B]
+        (pose, traj, goal, x0, yref ...); components 0 and 1 of each group become float32 (v - origin), the others
+        are converted. Returns the float32 tensor (out, when given)."""
+        v = map_values if map_values.dim() == 3 else map_values.unsqueeze(0)
+        n, c, B = v.shape
+        self._batch_of(v, 2)
+        res = out if out is not None else torch.empty(map_values.shape, dtype=F32, device=self.device)
+        check(lib().nmpc_batch_to_frame(self._h, B, _ptr(v, F64, None, "map_values"), n, c,
+                                        _ptr(res, F32, tuple(map_values.shape), "out"), _stream(stream)),
+              "nmpc_batch_to_frame")
+        return res
+
+    def from_frame(self, frame_values, out=None, stream=None):
+        """Frame values back into map coordinates (nmpc_batch_from_frame): frame_values float32 [n][c][B] or [c][B]
+        (x1, xtraj, traj_out ...); returns the float64 tensor (out, when given)."""
+        v = frame_values if frame_values.dim() == 3 else frame_values.unsqueeze(0)
+        n, c, B = v.shape
+        self._batch_of(v, 2)
+        res = out if out is not None else torch.empty(frame_values.shape, dtype=F64, device=self.device)
+        check(lib().nmpc_batch_from_frame(self._h, B, _ptr(v, F32, None, "frame_values"), n, c,
+                                          _ptr(res, F64, tuple(frame_values.shape), "out"), _stream(stream)),
+              "nmpc_batch_from_frame")
+        return res
+
+    def robot_frame(self):
+        """View of the frame table [2][cap] (float64), or None while it is off (nmpc_batch_robot_frame)."""
+        tb, stride = ctypes.c_void_p(), ctypes.c_int()
+        check(lib().nmpc_batch_robot_frame(self._h, ctypes.byref(tb), ctypes.byref(stride)), "nmpc_batch_robot_frame")
+        return _DeviceView(tb.value, (2, stride.value), self.device, F64) if tb.value else None
+
+    def clear_robot_frame(self, stream=None):
+        """Move every robot's iterate back to map coordinates and turn the frame table off (one launch)."""
+        check(lib().nmpc_batch_clear_robot_frame(self._h, _stream(stream)), "nmpc_batch_clear_robot_frame")
+
     def save_state(self):
         """Device copies of everything a solve reads from the handle: iterate, carried refs, warm start (five
         tensors), then the per-robot table as a tensor when it is on, then the stage table as
-        {"stage_bounds": bytes} and the model table as {"robot_model": tensor} when they are on."""
+        {"stage_bounds": bytes}, the model table as {"robot_model": tensor} and the frame table as {"robot_frame":
+        tensor} when they are on."""
         saved = [v.to_tensor() for v in self.state() + self.warm_state()]
         for name, view, _, _ in self._tables():
             v = view()
@@ -283,10 +341,10 @@ class BatchSolver:
         return saved
 
     def restore_state(self, saved):
-        for v, t in zip(self.state() + self.warm_state(), saved):
-            v.copy_from(t)
-        # every table as the checkpoint has it: loaded when it is there, else switched off. The model table first, the
-        # per-robot table last (the stage table's bytes replace its first fill, whatever that took from the latter)
+        # every table as the checkpoint has it: loaded when it is there, else switched off. The frame table first, before
+        # the iterate that is relative to it (its writer and its clear move the iterate that is resident then), then the
+        # model table, the per-robot table last (the stage table's bytes replace its first fill, whatever that took
+        # from the latter)
         have = {}
         for e in saved[5:]:
             have.update(e if isinstance(e, dict) else {None: e})
@@ -296,6 +354,8 @@ class BatchSolver:
                 torch.cuda.synchronize()
             else:
                 clear()
+        for v, t in zip(self.state() + self.warm_state(), saved):
+            v.copy_from(t)
 
     def _tables(self):
         """The per-robot device tables in save_state's order: the key of the table's entry in a checkpoint (None: a
@@ -315,7 +375,9 @@ class BatchSolver:
         return [(None, self.robot_params, load_params, self.clear_robot_params),
                 ("stage_bounds", self.stage_bounds, load_stage, self.clear_stage_bounds),
                 ("robot_model", self.robot_model, lambda t: self.set_robot_model(t.contiguous()),
-                 self.clear_robot_model)]
+                 self.clear_robot_model),
+                ("robot_frame", self.robot_frame, lambda t: self.set_robot_frame(t.contiguous()),
+                 self.clear_robot_frame)]
 
     def _rp_fields(self):
         """the per-robot table's fields and their rows, in the table's order"""

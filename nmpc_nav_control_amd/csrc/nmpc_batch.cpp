@@ -17,12 +17,15 @@ using namespace nmpc;
 
 // One per-robot device table of a handle (DESIGN.md "Per-robot device tables"): off until its first writer, which
 // allocates it and fills it with what the launches used until then (table_ready); nmpc_batch_clear_* switches it off
-// and keeps the allocation for the next writer, which refills it
+// and keeps the allocation for the next writer, which refills it. Sized in floats; the frame table's doubles count as
+// two each and are reached through view64 / p64 (a device allocation is aligned for either)
 struct DevTable {
     float* p = nullptr;
     size_t floats = 0;  // its size, fixed at create
     bool on = false;    // launches read it
     float* view() const { return on ? p : nullptr; }  // what launches and the view functions see
+    double* p64() const { return reinterpret_cast<double*>(p); }
+    double* view64() const { return on ? p64() : nullptr; }
 };
 
 struct nmpc_batch {
@@ -72,8 +75,9 @@ struct nmpc_batch {
     // the per-robot device tables, read by the launches (resident_args) while they are on:
     // bounds and weights (nmpc_batch_set_robot_params), [rp.off[kRpFields]][capacity];
     // stage-varying bounds (nmpc_batch_set_stage_bounds), (N + 1) * sb_rows * capacity floats (sb_at, nmpc_kernels.hpp);
-    // model parameters (nmpc_batch_set_robot_model), [np][capacity], which the harness plant reads too (fleet_sim)
-    DevTable rparams, sbounds, rmodel;
+    // model parameters (nmpc_batch_set_robot_model), [np][capacity], which the harness plant reads too (fleet_sim);
+    // map frames (nmpc_batch_set_robot_frame), fp64 [2][capacity]: every robot's origin x, then y
+    DevTable rparams, sbounds, rmodel, rframe;
     RpRows rp{};
     int np = 0;
 };
@@ -341,6 +345,7 @@ KArgs resident_args(const nmpc_batch* b, int B)
     a.rparams = b->rparams.view();
     a.sbounds = b->sbounds.view();
     a.rmodel = b->rmodel.view();
+    a.set_origin(b->rframe.view64());  // (in traj's slot: the launches that are given their poses overwrite it)
     return a;
 }
 
@@ -387,6 +392,21 @@ int rm_table(nmpc_batch* b, hipStream_t s)
         for (int i = 0; i < b->np; i++) col.v[i] = b->kp.p[i];
         return launch_rows_fill(t, b->capacity, b->np, col, s);
     });
+}
+
+// the frame table's fill: every origin (0, 0), where the launches took the positions to be until now
+int rf_table(nmpc_batch* b, hipStream_t s)
+{
+    return table_ready(b->rframe, "robot_frame fill launch",
+                       [&](float* t) { return hipMemsetAsync(t, 0, sizeof(float) * b->rframe.floats, s); });
+}
+
+// the frame table's one writer launch (nmpc_batch_set_robot_frame, _recentre, _clear_robot_frame: launch_frame_set)
+hipError_t frame_set(nmpc_batch* b, int B, const double* origin, const double* pose_map, double radius,
+                     unsigned char* moved, const unsigned char* mask, hipStream_t s)
+{
+    return launch_frame_set(b->rframe.p64(), b->capacity, B, b->xbar, b->prm.N, b->nx, origin, pose_map, radius, moved,
+                            mask, s);
 }
 
 SbDims sb_dims(const nmpc_batch* b) { return SbDims{b->prm.N, b->capacity, b->nbx, b->nbu}; }
@@ -605,6 +625,7 @@ int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** o
     b->rparams.floats = (size_t)b->rp.off[kRpFields] * (size_t)capacity;
     b->sbounds.floats = (size_t)(prm->N + 1) * (size_t)sb_rows(b->nbx, b->nbu) * (size_t)capacity;
     b->rmodel.floats = (size_t)b->np * (size_t)capacity;
+    b->rframe.floats = 4 * (size_t)capacity;  // [2][capacity] doubles
     if (const char* sv = std::getenv("NMPC_AMD_SCHED")) {  // off | auto | sorted | interleaved
         const char* names[5] = {"off", "auto", "sorted", "interleaved", "spread"};
         for (int i = 0; i < 5; i++)
@@ -669,7 +690,7 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->node_active);
     (void)hipFree(b->node_n);
     (void)hipFree(b->node_status);
-    for (const DevTable* t : {&b->rparams, &b->sbounds, &b->rmodel}) (void)hipFree(t->p);
+    for (const DevTable* t : {&b->rparams, &b->sbounds, &b->rmodel, &b->rframe}) (void)hipFree(t->p);
     delete b;
     return NMPC_OK;
 }
@@ -848,8 +869,9 @@ int nmpc_batch_follow_path(nmpc_batch* b, int B, const float* pose, const float*
     }
     hipStream_t s = (hipStream_t)stream;
     // the search starts at the robot's progress so far and writes nearest_u over it
-    int rc = hip_err(launch_path_nearest(B, segs, seg_stride, nseg, pose, path_u, nullptr,
-                                         b->prm.model == NMPC_MODEL_OMNI4AMR ? 1 : 0, path_u, nullptr, err, s),
+    // (under a frame the pose is the robot's frame value and the search runs at its map position)
+    int rc = hip_err(launch_path_nearest(B, segs, seg_stride, nseg, pose, b->rframe.view64(), b->capacity, path_u,
+                                         nullptr, b->prm.model == NMPC_MODEL_OMNI4AMR ? 1 : 0, path_u, nullptr, err, s),
                      "path_nearest launch");
     if (rc) return rc;
     rc = nmpc_batch_run_path(b, B, pose, vel, steer, segs, seg_stride, nseg, path_u, sample_period, is_holonomic,
@@ -936,6 +958,8 @@ int node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_
     g.mode = mode;
     g.pose = pose;
     g.goal = goal;
+    g.origin = b->rframe.view64();
+    g.ostride = b->capacity;
     g.segs = paths ? segs : nullptr;
     g.nseg = (paths && !q) ? nseg : nullptr;
     g.path_u = paths ? path_u : nullptr;
@@ -1112,6 +1136,70 @@ int nmpc_batch_robot_model(nmpc_batch* b, float** table, int* rows, int* stride)
 
 int nmpc_batch_clear_robot_model(nmpc_batch* b) { return table_clear(b, &nmpc_batch::rmodel); }
 
+int nmpc_batch_set_robot_frame(nmpc_batch* b, int B, const double* origin, const unsigned char* mask, void* stream)
+{
+    return table_write(b, B, origin ? nullptr : "robot frame: origin is NULL", rf_table, stream, "robot_frame launch",
+                       [&](hipStream_t s) { return frame_set(b, B, origin, nullptr, 0.0, nullptr, mask, s); });
+}
+
+int nmpc_batch_recentre(nmpc_batch* b, int B, const double* pose_map, double radius, const unsigned char* mask,
+                        unsigned char* moved, void* stream)
+{
+    return table_write(b, B, pose_map ? nullptr : "recentre: pose_map is NULL", rf_table, stream, "recentre launch",
+                       [&](hipStream_t s) { return frame_set(b, B, nullptr, pose_map, radius, moved, mask, s); });
+}
+
+namespace {
+// the checks nmpc_batch_to_frame and _from_frame share, those that need no handle first; *go: there is work
+int frame_map_check(const nmpc_batch* b, int B, const void* src, const void* dst, int n, int c, bool* go)
+{
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (n < 0) return set_err(NMPC_ERR_ARG, "frame: n must be >= 0");
+    if (c < 2) return set_err(NMPC_ERR_ARG, "frame: c must be >= 2");
+    if (!src || !dst) return set_err(NMPC_ERR_ARG, "frame: the input and output arrays are required");
+    if (const int rc = check_batch(b, B)) return rc;
+    *go = B > 0 && n > 0;
+    return NMPC_OK;
+}
+}  // namespace
+
+int nmpc_batch_to_frame(nmpc_batch* b, int B, const double* map, int n, int c, float* out, void* stream)
+{
+    bool go = false;
+    if (const int rc = frame_map_check(b, B, map, out, n, c, &go)) return rc;
+    if (!go) return NMPC_OK;
+    return hip_err(launch_to_frame(b->rframe.view64(), b->capacity, B, n, c, map, out, (hipStream_t)stream),
+                   "to_frame launch");
+}
+
+int nmpc_batch_from_frame(nmpc_batch* b, int B, const float* in, int n, int c, double* map, void* stream)
+{
+    bool go = false;
+    if (const int rc = frame_map_check(b, B, in, map, n, c, &go)) return rc;
+    if (!go) return NMPC_OK;
+    return hip_err(launch_from_frame(b->rframe.view64(), b->capacity, B, n, c, in, map, (hipStream_t)stream),
+                   "from_frame launch");
+}
+
+int nmpc_batch_robot_frame(nmpc_batch* b, double** table, int* stride)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (table) *table = b->rframe.view64();
+    if (stride) *stride = b->capacity;
+    return NMPC_OK;
+}
+
+int nmpc_batch_clear_robot_frame(nmpc_batch* b, void* stream)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (!b->rframe.on) return NMPC_OK;
+    // every robot's iterate back to map coordinates (origin zero for the whole capacity), then off
+    const int rc = hip_err(frame_set(b, b->capacity, nullptr, nullptr, 0.0, nullptr, nullptr, (hipStream_t)stream),
+                           "robot_frame clear launch");
+    if (rc == NMPC_OK) b->rframe.on = false;
+    return rc;
+}
+
 int nmpc_batch_set_record_layout(nmpc_batch* b, int layout)
 {
     if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
@@ -1232,8 +1320,9 @@ int nmpc_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, cons
     if (!segs || !nseg || !pose) return set_err(NMPC_ERR_ARG, "segs, nseg and pose are required");
     if (!nearest_u) return set_err(NMPC_ERR_ARG, "nearest_u is required");
     if (seg_stride < 1) return set_err(NMPC_ERR_ARG, "seg_stride < 1");
-    return hip_err(launch_path_nearest(B, segs, seg_stride, nseg, pose, u_range, u_range ? u_range + B : nullptr,
-                                       holonomic_heading ? 1 : 0, nearest_u, near, err, (hipStream_t)stream),
+    return hip_err(launch_path_nearest(B, segs, seg_stride, nseg, pose, nullptr, 0, u_range,
+                                       u_range ? u_range + B : nullptr, holonomic_heading ? 1 : 0, nearest_u, near, err,
+                                       (hipStream_t)stream),
                    "path_nearest launch");
 }
 

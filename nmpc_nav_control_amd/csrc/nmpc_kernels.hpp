@@ -58,6 +58,12 @@ struct KArgs {
     const double* nearest_u;        // [B]
     double period;
     float* traj_out;                // [N+1][3][B] or nullptr: the poses the march produced
+    // Per-robot map frames (robot_tables.hip): the handle's frame table, fp64 [2][sstride], every robot's origin x, then
+    // y; nullptr: the table is off and the march's poses stay in map coordinates. Only a launch that marches reads it,
+    // and such a launch is given no poses, so the table travels in traj's slot: the launches without a march keep their
+    // argument layout, and with it their device code
+    void set_origin(const double* o) { traj = reinterpret_cast<const float*>(o); }
+    __host__ __device__ const double* origin() const { return reinterpret_cast<const double*>(traj); }
     // outputs (each may be nullptr)
     float* u0;     // [NU][B]
     float* x1;     // [NX][B]
@@ -168,7 +174,7 @@ hipError_t launch_node_order(const int* key, const unsigned char* active, int B,
 hipError_t launch_init_iterate(float* xbar, float* ubar, float* carried, unsigned char* warm, int B, int stride, int N,
                                int nx, int nu, int nbx, int mode, hipStream_t stream);
 hipError_t launch_forget_warm(unsigned char* warm, const unsigned char* mask, int B, hipStream_t stream);
-// The writers of the three per-robot device tables (robot_tables.hip), each one launch; mask: the robots with
+// The writers of the per-robot device tables (robot_tables.hip), each one launch; mask: the robots with
 // mask[i] != 0 (nullptr: all of the first B).
 // Row-major tables [rows][cap] (the per-robot table, the model table): fill: every robot's column = col (the first
 // `cap` robots); set: the rows of the non-NULL fields of a list of kFields fields (field f: the rows [off[f],
@@ -196,14 +202,30 @@ hipError_t launch_sb_limits(float* sb, const SbDims& d, int B, int tric, const f
                             const float* alpha_min, const float* alpha_max, const float* dalpha_max,
                             const unsigned char* mask, hipStream_t stream);
 hipError_t launch_sb_shift(float* sb, const SbDims& d, int B, int n, const unsigned char* mask, hipStream_t stream);
+// The frame table fr [2][cap] (fp64: every robot's origin x, then y) and the resident iterate's position rows.
+// frame_set: the masked robots of the first B take a new origin and the x and y row of every stage of xbar
+// ([(N+1)*nx][cap]) becomes (float)((double)x + (o_old - o_new)). The new origin is origin[2][B]; or, with pose_map
+// ([>= 2 rows][B]) given instead, rint of the robot's map position where that is finite and farther than radius from
+// the old origin in x or y (moved[i] = 1; the others stay, moved[i] = 0; moved [B] or nullptr); or, with neither, zero.
+// to_frame / from_frame: arrays [n][c][B], components 0 and 1 of each group (float)(v - origin) / (double)v + origin,
+// the others converted; fr may be nullptr (the table is off: origin zero)
+hipError_t launch_frame_set(double* fr, int cap, int B, float* xbar, int N, int nx, const double* origin,
+                            const double* pose_map, double radius, unsigned char* moved, const unsigned char* mask,
+                            hipStream_t stream);
+hipError_t launch_to_frame(const double* fr, int cap, int B, int n, int c, const double* map, float* out,
+                           hipStream_t stream);
+hipError_t launch_from_frame(const double* fr, int cap, int B, int n, int c, const float* in, double* map,
+                             hipStream_t stream);
 hipError_t launch_path_discretize(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
                                   const double* nearest_u, double period, int num_poses, int holo, float* traj,
                                   double* traj64, hipStream_t stream);
 // nearest path point of every robot (path_nearest.hip): lo / hi [B] bounds of the search range, each may be nullptr;
-// lo may alias nearest_u (a robot's bound is read before its result is written)
+// lo may alias nearest_u (a robot's bound is read before its result is written). origin [2][ostride]: a handle's frame
+// table, the pose then being in each robot's frame (the search runs at (double)pose + origin), or nullptr
 hipError_t launch_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
-                               const float* pose, const double* lo, const double* hi, int holo, double* nearest_u,
-                               double* near, double* err, hipStream_t stream);
+                               const float* pose, const double* origin, int ostride, const double* lo,
+                               const double* hi, int holo, double* nearest_u, double* near, double* err,
+                               hipStream_t stream);
 // the path-error check of nmpc_batch_follow_path on err [2][B]: off_path [B] (or nullptr) and the stop command in cmd
 // [3][B] (or nullptr) for the robots whose error reaches a threshold whose comparison is on (use_pos / use_ori)
 hipError_t launch_path_guard(int B, const double* err, double max_pos, double max_ori, int use_pos, int use_ori,
@@ -218,6 +240,10 @@ struct NodeGateArgs {
     unsigned char* mode;
     const float* pose;
     const float* goal;
+    // the handle's frame table [2][ostride], or nullptr while it is off: pose, goal and the reference poses are in each
+    // robot's frame, the segments in map coordinates
+    const double* origin;
+    int ostride;
     const nmpc_path_segment* segs;
     const int* nseg;
     double* path_u;

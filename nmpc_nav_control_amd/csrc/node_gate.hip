@@ -128,10 +128,15 @@ __global__ void __launch_bounds__(kGateBlock) k_node_gate(NodeGateArgs g)
     if (m == NMPC_NODE_FOLLOW_PATH && !(g.segs && (Queue || g.nseg) && g.path_u)) m = NMPC_NODE_ERROR;
     const bool follow = m == NMPC_NODE_FOLLOW_PATH;
     double px = 0.0, py = 0.0, pth = 0.0;
+    double mx = 0.0, my = 0.0;  // the robot in map coordinates, where its path is (px, py: in its frame, as its goal)
     if (live) {
-        px = (double)g.pose[i];
-        py = (double)g.pose[Bn + i];
+        px = mx = (double)g.pose[i];
+        py = my = (double)g.pose[Bn + i];
         pth = (double)g.pose[2 * Bn + i];
+        if (g.origin) {
+            mx += g.origin[i];
+            my += g.origin[(size_t)g.ostride + i];
+        }
     }
     const nmpc_path_segment* S = g.segs + (follow ? i * (size_t)g.seg_stride : 0);
     int n;
@@ -150,7 +155,7 @@ __global__ void __launch_bounds__(kGateBlock) k_node_gate(NodeGateArgs g)
     }
     // (the rows of a wave are together again here: the search's shuffles need all 64 lanes)
     const double lo_in = n >= 1 ? g.path_u[i] : nan;
-    NearResult R = near_search(S, n, j, px, py, pth, lo_in, nan, g.holo_err);
+    NearResult R = near_search(S, n, j, mx, my, pth, lo_in, nan, g.holo_err);
     // (no cross-lane operation below; every decision is the same in the 16 lanes of a row)
     if constexpr (Queue) {
         if (n >= 1) {
@@ -266,7 +271,14 @@ __global__ void __launch_bounds__(64) k_node_march(NodeGateArgs g)
     const int count = path_march(S, n, g.path_u[i], np.sample_period, N + 1,
                                  [&](int q, double u) { emit_u[q * es] = u; });
     // the end test against the last pose (the path end when the march stopped short: the padding of :58-63)
-    const double px = (double)g.pose[i], py = (double)g.pose[Bn + i], pth = (double)g.pose[2 * Bn + i];
+    // (the robot and the last pose both in map coordinates; the reference poses leave in the robot's frame)
+    const double ox = g.origin ? g.origin[i] : 0.0, oy = g.origin ? g.origin[(size_t)g.ostride + i] : 0.0;
+    const double pth = (double)g.pose[2 * Bn + i];
+    double px = (double)g.pose[i], py = (double)g.pose[Bn + i];
+    if (g.origin) {
+        px += ox;
+        py += oy;
+    }
     double lx, ly, lth;
     path_pose(S, n, (N < count) ? emit_u[N * es] : (double)n, np.is_holonomic, &lx, &ly, &lth);
     const bool solve = !gate_arrived(np, px, py, pth, lx, ly, lth);
@@ -276,12 +288,13 @@ __global__ void __launch_bounds__(64) k_node_march(NodeGateArgs g)
         if (solve) {
             double x, y, th;
             path_pose(S, n, (q < count) ? emit_u[q * es] : (double)n, np.is_holonomic, &x, &y, &th);
-            g.traj[o] = (float)x;
-            g.traj[o + Bn] = (float)y;
+            const float fx = (float)(x - ox), fy = (float)(y - oy);
+            g.traj[o] = fx;
+            g.traj[o + Bn] = fy;
             g.traj[o + 2 * Bn] = (float)th;
             if (g.traj_out) {
-                g.traj_out[o] = (float)x;
-                g.traj_out[o + Bn] = (float)y;
+                g.traj_out[o] = fx;
+                g.traj_out[o + Bn] = fy;
                 g.traj_out[o + 2 * Bn] = (float)th;
             }
         } else if (g.traj_out) {

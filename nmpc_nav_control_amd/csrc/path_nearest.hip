@@ -17,7 +17,8 @@ namespace {
 constexpr int kNearBlock = 256;
 
 __global__ void __launch_bounds__(kNearBlock) k_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride,
-                                                             const int* nseg, const float* pose, const double* lo,
+                                                             const int* nseg, const float* pose,
+                                                             const double* origin, int ostride, const double* lo,
                                                              const double* hi, int holo, double* nearest_u,
                                                              double* near, double* err)
 {
@@ -33,6 +34,10 @@ __global__ void __launch_bounds__(kNearBlock) k_path_nearest(int B, const nmpc_p
     if (live) {
         px = (double)pose[i];
         py = (double)pose[Bn + i];
+        if (origin) {  // a handle's frame: the pose is relative to the robot's origin, the path in map coordinates
+            px += origin[i];
+            py += origin[(size_t)ostride + i];
+        }
         pth = (double)pose[2 * Bn + i];
         lo_in = lo ? lo[i] : __builtin_nan("");
         hi_in = hi ? hi[i] : __builtin_nan("");
@@ -76,13 +81,14 @@ hipError_t launch_path_guard(int B, const double* err, double max_pos, double ma
 }
 
 hipError_t launch_path_nearest(int B, const nmpc_path_segment* segs, int seg_stride, const int* nseg,
-                               const float* pose, const double* lo, const double* hi, int holo, double* nearest_u,
-                               double* near, double* err, hipStream_t stream)
+                               const float* pose, const double* origin, int ostride, const double* lo,
+                               const double* hi, int holo, double* nearest_u, double* near, double* err,
+                               hipStream_t stream)
 {
     if (B <= 0) return hipSuccess;
     const unsigned blocks = (unsigned)(((size_t)B * 16 + kNearBlock - 1) / kNearBlock);
-    hipLaunchKernelGGL(k_path_nearest, dim3(blocks), dim3(kNearBlock), 0, stream, B, segs, seg_stride, nseg, pose, lo,
-                       hi, holo, nearest_u, near, err);
+    hipLaunchKernelGGL(k_path_nearest, dim3(blocks), dim3(kNearBlock), 0, stream, B, segs, seg_stride, nseg, pose,
+                       origin, ostride, lo, hi, holo, nearest_u, near, err);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// robot_tables.hip -- the writers of the handle's three per-robot device tables (DESIGN.md "Per-robot device tables",
+// robot_tables.hip -- the writers of the handle's four per-robot device tables (DESIGN.md "Per-robot device tables",
 // nmpc_batch.h):
 //   the per-robot table of bounds and weights, [rows][capacity] fp32, rows lbx ubx lbu ubu W W_e (RpRows,
 //   nmpc_kernels.hpp); both solve kernels read a robot's column in their prologue (lane_ctx / load_x0, sqp_steps.hpp);
@@ -6,7 +6,10 @@
 //   {d, tau_v, tau_a}); the solve kernels read a column in their prologue (robot_vals), the harness plant in its lead
 //   lane (fleet_sim.hip);
 //   the stage table, every robot's box at every stage, rows lbx ubx lbu ubu per stage and robot laid out by sb_at
-//   (nmpc_kernels.hpp); the solve kernels read a lane's pair of a stage in P0 (stage_box).
+//   (nmpc_kernels.hpp); the solve kernels read a lane's pair of a stage in P0 (stage_box);
+//   the frame table, [2][capacity] fp64, every robot's map origin x, then y; the launches that read path segments
+//   bridge a robot's frame and the map with it (the team kernel's march, node_gate.hip, path_nearest.hip), and its
+//   writer moves the resident iterate's position rows along, so that the iterate's map position stays.
 // Every writer is one elementwise launch on the caller's stream: x over robots in blocks of 256, thread i of a row, of
 // a (stage, row) or of a stage writes robot i (a row-major row's stores are coalesced), every index is checked against
 // B <= capacity, and nothing is read back or checked on the host.
@@ -156,6 +159,57 @@ __global__ void k_sb_shift(float* sb, SbDims d, int B, int n, const unsigned cha
     }
 }
 
+// ---- the frame table [2][cap], fp64 ---------------------------------------------------------------------------------
+// One thread per robot: it reads both of the robot's old origins before it writes either, decides (pose_map) from both
+// coordinates, and walks the stages of the iterate's x and y rows, so no other thread needs what it overwrites
+__global__ void k_frame_set(double* fr, int cap, int B, float* xbar, int N, int nx, const double* origin,
+                            const double* pose_map, double radius, unsigned char* moved, const unsigned char* mask)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    bool go = !mask || mask[i];
+    const double ox = fr[i], oy = fr[(size_t)cap + i];
+    double nx_o = 0.0, ny_o = 0.0;
+    if (pose_map) {
+        const double x = pose_map[i], y = pose_map[(size_t)B + i];
+        // (false on a NaN position or radius)
+        go = go && (fabs(x - ox) > radius || fabs(y - oy) > radius) && isfinite(x) && isfinite(y);
+        nx_o = rint(x);
+        ny_o = rint(y);
+        if (moved) moved[i] = go ? 1 : 0;
+    } else if (origin) {
+        nx_o = origin[i];
+        ny_o = origin[(size_t)B + i];
+    }
+    if (!go) return;
+    fr[i] = nx_o;
+    fr[(size_t)cap + i] = ny_o;
+    const double dx = ox - nx_o, dy = oy - ny_o;
+    for (int k = 0; k <= N; k++) {
+        float* const x = xbar + ((size_t)k * nx) * cap + i;
+        x[0] = (float)((double)x[0] + dx);
+        x[cap] = (float)((double)x[cap] + dy);
+    }
+}
+
+// element e of an array [n][c][B]: robot e % B, component (e / B) % c
+template <bool kTo>
+__global__ void k_frame_map(const double* fr, int cap, int B, int c, size_t total, const double* map_in,
+                            const float* frame_in, float* frame_out, double* map_out)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const int i = (int)(e % (size_t)B), comp = (int)((e / (size_t)B) % (size_t)c);
+    const double o = (fr && comp < 2) ? fr[(size_t)comp * cap + i] : 0.0;
+    if (kTo) {
+        const double v = map_in[e];
+        frame_out[e] = (float)(comp < 2 ? v - o : v);
+    } else {
+        const double v = (double)frame_in[e];
+        map_out[e] = comp < 2 ? v + o : v;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_rows_fill(float* table, int cap, int rows, const RpColumn& col, hipStream_t stream)
@@ -226,6 +280,43 @@ hipError_t launch_sb_shift(float* sb, const SbDims& d, int B, int n, const unsig
     if (B <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_sb_shift, grid_of(B, sb_rows(d.nbx, d.nbu)), dim3(kThreads), 0, stream, sb, d, B, n, mask);
     return hipGetLastError();
+}
+
+hipError_t launch_frame_set(double* fr, int cap, int B, float* xbar, int N, int nx, const double* origin,
+                            const double* pose_map, double radius, unsigned char* moved, const unsigned char* mask,
+                            hipStream_t stream)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_frame_set, grid_of(B), dim3(kThreads), 0, stream, fr, cap, B, xbar, N, nx, origin, pose_map,
+                       radius, moved, mask);
+    return hipGetLastError();
+}
+
+namespace {
+template <bool kTo>
+hipError_t launch_frame_map(const double* fr, int cap, int B, int n, int c, const double* map_in, const float* frame_in,
+                            float* frame_out, double* map_out, hipStream_t stream)
+{
+    const size_t total = (size_t)n * (size_t)c * (size_t)B;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + kThreads - 1) / kThreads;
+    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_frame_map<kTo>, dim3((unsigned)blocks), dim3(kThreads), 0, stream, fr, cap, B, c, total,
+                       map_in, frame_in, frame_out, map_out);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_to_frame(const double* fr, int cap, int B, int n, int c, const double* map, float* out,
+                           hipStream_t stream)
+{
+    return launch_frame_map<true>(fr, cap, B, n, c, map, nullptr, out, nullptr, stream);
+}
+
+hipError_t launch_from_frame(const double* fr, int cap, int B, int n, int c, const float* in, double* map,
+                             hipStream_t stream)
+{
+    return launch_frame_map<false>(fr, cap, B, n, c, nullptr, in, nullptr, map, stream);
 }
 
 }  // namespace nmpc

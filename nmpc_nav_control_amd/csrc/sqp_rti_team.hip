@@ -206,15 +206,19 @@ __global__ __launch_bounds__(256, 1) void k_sqp_rti_team(KParams P, KArgs a)
             const int cnt = path_march(S, n, a.nearest_u[inst], a.period, N + 1, [&](int j, double su) { my_u[j] = su; });
             for (int j = cnt; j <= N; j++) my_u[j] = (double)n;
         }
+        // the robot's frame (nmpc_batch_set_robot_frame): the map poses move into it in fp64, before their one rounding
+        const double* const fr = a.origin();
+        const double ox = fr ? fr[inst] : 0.0, oy = fr ? fr[(size_t)a.sstride + inst] : 0.0;
         for (int j = r; j <= N; j += 16) {
             double px, py, pt;
             path_pose(S, n, my_u[j], a.holo, &px, &py, &pt);
-            my_traj[j * 3 + 0] = (float)px;
-            my_traj[j * 3 + 1] = (float)py;
+            const float fx = (float)(px - ox), fy = (float)(py - oy);
+            my_traj[j * 3 + 0] = fx;
+            my_traj[j * 3 + 1] = fy;
             my_traj[j * 3 + 2] = (float)pt;
             if (a.traj_out) {
-                a.traj_out[((size_t)j * 3 + 0) * Bn + inst] = (float)px;
-                a.traj_out[((size_t)j * 3 + 1) * Bn + inst] = (float)py;
+                a.traj_out[((size_t)j * 3 + 0) * Bn + inst] = fx;
+                a.traj_out[((size_t)j * 3 + 1) * Bn + inst] = fy;
                 a.traj_out[((size_t)j * 3 + 2) * Bn + inst] = (float)pt;
             }
         }

@@ -3,7 +3,7 @@
 table off and with the table on holding the handle's own values, i.e. the same QPs, and the cost of one launch of each
 of the table's writers. One JSON line per measurement.
 
-usage: python tools/bench_tables.py --table robot_params|stage_bounds|robot_model
+usage: python tools/bench_tables.py --table robot_params|stage_bounds|robot_model|frame
                                     [--config metric|diff1024|omni4|tric] [--model diff] [--batch 4096] [--N 40]
                                     [--steps 100] [--warmup 240] [--repeats 3]
 --config names a (model, batch, N) of bench.py (default metric: diff, 4096, 40); --model, --batch and --N replace its
@@ -14,8 +14,15 @@ state; `rate` is robot ticks per second over the timed steps (solve + plant step
   robot_model   off, uniform (the handle's p in every column), rule (the mixed fleet of tests/robot_model_cases.py,
                 whose factors are imported from there; the harness plant steps each robot with its own column, so
                 this closed loop is the mixed fleet's);                     writer: set_robot_model
+  frame         the run-mode closed loop reads nothing of the frame table, so its variants are the launches that
+                do: a follow_path tick and a queue node tick (every robot in FOLLOW_PATH) of robots standing beside
+                seeded paths, with the table off and with it on (tests/frame_cases.py's four origins mixed robot by
+                robot, the segments moved there in fp64, the same fp32 poses); `us_per_tick` is the mean over the
+                timed ticks, launched back to back;   writers: set_robot_frame, recentre (a radius that moves every
+                robot, then one that moves none), to_frame and from_frame of a pose and of a trajectory
 The writers are timed on 4096 robots with a mask on half of them: mean over 200 back-to-back launches."""
 import argparse
+import itertools
 import json
 import os
 import sys
@@ -24,9 +31,13 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from nmpc_nav_control_amd.batch import BatchSolver  # noqa: E402
+from nmpc_nav_control_amd.batch import BatchSolver, NodeParams  # noqa: E402
 from nmpc_nav_control_amd.fleet import Fleet  # noqa: E402
 from nmpc_nav_control_amd.scenario import DEFAULT_SEED, PARAMS  # noqa: E402
+from nmpc_nav_control_amd.path import PathQueue  # noqa: E402
+from tests import frame_cases  # noqa: E402  (the origins, stated once)
+from tests.path_cases import random_paths  # noqa: E402
+from tests.path_nearest_ref import near_err  # noqa: E402
 from tests.robot_model_cases import P0, P1, P2  # noqa: E402  (the rule's factors, stated once)
 
 CONFIGS = {"metric": ("diff", 4096, 40), "diff1024": ("diff", 1024, 40), "omni4": ("omni4", 4096, 40),
@@ -76,6 +87,28 @@ def rm_writers(s, B, dev):
              dict(model=s.model, B=B, N=s.N, table_bytes=4 * s.np * B))]
 
 
+def fr_writers(s, B, dev):
+    per = torch.from_numpy(frame_cases.per_robot(B).T.copy()).to(dev)
+    mask, moved = half_mask(B, dev), torch.zeros(B, dtype=torch.uint8, device=dev)
+    pose = per.clone()
+    pose[0] += 0.25
+    turns = itertools.cycle((per + 100.0, pose))  # every launch moves every masked robot: 100 m out, then back
+    traj = torch.zeros(s.N + 1, 3, B, dtype=torch.float64, device=dev)
+    traj[:, :2] = per[None]
+    pose32, traj32 = torch.zeros(3, B, device=dev), torch.zeros(s.N + 1, 3, B, device=dev)
+    pose3 = torch.cat([pose, torch.zeros(1, B, dtype=torch.float64, device=dev)]).contiguous()
+    p64, t64 = torch.zeros_like(pose3), torch.zeros_like(traj)
+    keys = dict(model=s.model, B=B, N=s.N, table_bytes=16 * B)
+    return [("set_robot_frame launch", lambda: s.set_robot_frame(per, mask=mask), keys),
+            ("recentre launch, every masked robot moves",
+             lambda: s.recentre(next(turns), 2.0, mask=mask, moved=moved), keys),
+            ("recentre launch, no robot moves", lambda: s.recentre(pose, 1e9, mask=mask, moved=moved), keys),
+            ("to_frame launch, pose [3][B]", lambda: s.to_frame(pose3, out=pose32), keys),
+            ("from_frame launch, pose [3][B]", lambda: s.from_frame(pose32, out=p64), keys),
+            ("to_frame launch, traj [N+1][3][B]", lambda: s.to_frame(traj, out=traj32), keys),
+            ("from_frame launch, traj [N+1][3][B]", lambda: s.from_frame(traj32, out=t64), keys)]
+
+
 # per table: the closed loop's variants (label -> how the fleet's solver gets the table, None: off) and its writers
 # (what, one launch, the line's own keys; the first one's first call allocates and fills the table)
 TABLES = {
@@ -83,6 +116,7 @@ TABLES = {
     "stage_bounds": (dict(off=None, on=lambda s, B, dev: s.shift_stage_bounds(0)), sb_writers),
     "robot_model": (dict(off=None, uniform=lambda s, B, dev: s.set_robot_model(model_table(s, B, False, dev)),
                          rule=lambda s, B, dev: s.set_robot_model(model_table(s, B, True, dev))), rm_writers),
+    "frame": (dict(off=False, on=True), fr_writers),
 }
 
 
@@ -103,6 +137,64 @@ def timed(model, B, N, steps, warmup, label, fill, dev):
     fails = int((f.status != 0).sum().item())
     return dict(model=model, B=B, N=N, table=label, steps=steps, ms_per_step=round(ms / steps, 4),
                 rate=round(B * steps / ms * 1e3, 1), failed_last_tick=fails, plan=f.solver.plan_ex(B, "run")["kernel"])
+
+
+def path_fleet(B, S=4, seed=DEFAULT_SEED):
+    """robots beside the start of seeded forward paths (as tests/test_gpu_path_nearest.py:follow_case): segs [B][S][16],
+    nseg [B], pose and vel [B][3] (fp32)"""
+    rng = np.random.default_rng(seed)
+    segs, nseg, nu = random_paths(B, seed=seed, max_segs=S, reverse_frac=0.0)
+    pose = np.zeros((B, 3), np.float32)
+    for i in range(B):
+        en, _ = near_err(segs[i], int(nseg[i]), rng.uniform(0, 0.3), (0.0, 0.0, 0.0))
+        pose[i] = (en[0] + rng.uniform(-0.1, 0.1), en[1] + rng.uniform(-0.1, 0.1), en[2] + rng.uniform(-0.2, 0.2))
+    vel = np.zeros((B, 3), np.float32)
+    vel[:, 0] = rng.uniform(0.0, 0.5, B)
+    return segs, nseg, pose, vel
+
+
+def timed_path_ticks(model, B, N, steps, warmup, label, on, dev):
+    """the two launches that read the frame table, each timed over `steps` back-to-back ticks of a standing fleet"""
+    segs, nseg, pose, vel = path_fleet(B)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    per = frame_cases.per_robot(B)
+    S = segs.shape[1]
+    z = lambda *sh, dt=torch.float32: torch.zeros(*sh, dtype=dt, device=dev)  # noqa: E731
+    for what in ("follow_path", "node_tick_queue"):
+        s = BatchSolver(model, N, B, device=dev)
+        sg = d(frame_cases.move_segs(segs, per) if on else segs)
+        if on:
+            s.set_robot_frame(d(per.T.copy()))
+            s.init_iterate()
+        P, V, ns = d(pose.T), d(vel.T), d(nseg)
+        out = dict(cmd=z(3, B), u0=z(s.nu, B), status=z(B, dt=torch.int32), qp_iter=z(B, dt=torch.int32))
+        traj, err = z(N + 1, 3, B), z(2, B, dt=torch.float64)
+        if what == "follow_path":
+            u = z(B, dt=torch.float64)
+            tick = lambda: s.follow_path(P, V, sg, ns, u, 1 / 40, err=err, traj_out=traj, **out)  # noqa: E731
+        else:
+            q = PathQueue(B, S, device=dev)
+            q.segs.copy_(torch.nan_to_num(sg))
+            q.npart.copy_(ns)
+            mode, ev = torch.full((B,), 2, dtype=torch.uint8, device=dev), z(B, dt=torch.uint8)  # NODE_FOLLOW_PATH
+            n, rs = z(1, dt=torch.int32), z(B, dt=torch.uint8)
+            npar = NodeParams.default(max_pos_err=float("inf"), max_ori_err=float("inf"), final_pos_err=0.0)
+
+            def tick():
+                s.node_tick_queue(npar, q, mode, P, V, reset=rs, event=ev, err=err, traj_out=traj, n_solved=n, **out)
+        for _ in range(warmup):
+            tick()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(steps):
+            tick()
+        b.record()
+        torch.cuda.synchronize()
+        ms = a.elapsed_time(b)
+        yield dict(model=model, B=B, N=N, table=label, what=what + " tick", steps=steps,
+                   us_per_tick=round(ms / steps * 1e3, 2), rate=round(B * steps / ms * 1e3, 1),
+                   failed_last_tick=int((out["status"] != 0).sum().item()))
 
 
 def writer_launches(writers, model, N, dev, reps=200):
@@ -138,6 +230,10 @@ def main():
     dev = torch.device("cuda:0")
     for rep in range(args.repeats):
         for label, fill in variants.items():
+            if args.table == "frame":
+                for r in timed_path_ticks(model, B, N, args.steps, args.warmup, label, fill, dev):
+                    print(json.dumps(dict(r, repeat=rep)), flush=True)
+                continue
             r = timed(model, B, N, args.steps, args.warmup, label, fill, dev)
             print(json.dumps(dict(r, **tag, repeat=rep)), flush=True)
     for r in writer_launches(writers, model, N, dev):
