@@ -262,8 +262,9 @@ int nmpc_node_params_default(nmpc_node_params* np);
  * Out of scope here: the upcoming_path_ queue, the velocity-sign split of processPathBuffers (:576-595) and the hop
  * to the next queued path at :686-690. A robot's list is one active path, and on ARRIVED the caller hands the robot
  * its next part and sets reset[i]; nmpc_batch_node_tick_queue below keeps the whole path set on the device instead.
- * Out of scope for both (the caller's, on the host): getInputData (the TF lookups and the finite-difference
- * velocity). */
+ * Both ticks start after getInputData (:545-553): pose, vel and steer are its results. That first line of mainCycle
+ * has a stage of its own, nmpc_batch_node_input below, and nmpc_batch_node_cycle runs the stage and a tick in one
+ * call, from fp64 map coordinates to the command. */
 int nmpc_batch_node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, unsigned char* mode, const float* pose,
                          const float* vel, const float* steer, const float* goal, const nmpc_path_segment* segs,
                          int seg_stride, const int* nseg, double* path_u, unsigned char* reset, unsigned char* event,
@@ -328,6 +329,108 @@ int nmpc_batch_node_tick_queue(nmpc_batch* b, int B, const nmpc_node_params* np,
                                unsigned char* reset, unsigned char* event, double* err, float* traj_out,
                                int* n_solved, float* cmd, float* u0, int* status, int* qp_iter, float* qp_res,
                                void* stream);
+
+/* The node's input stage, getInputData (NMPCNavControlROS.cpp:545-553), on the device: per robot a history of
+ * localisation samples (the TF buffer of base_frame in the frame the robot's goal or path is expressed in), the pose
+ * with the heading hack of getRobotPose (:401-436), the finite-difference body velocity of getRobotVel (:438-484), the
+ * data ages, and the conversion of pose and goal into the robot's map frame (nmpc_batch_set_robot_frame), with the
+ * recentre decision in the same launch. Everything here is fp64 in map coordinates with int64 nanosecond stamps; the
+ * outputs are the fp32 frame values the ticks above take.
+ *
+ * nmpc_batch_enable_input allocates the state, per handle and on demand like the tables, instance-minor:
+ *   stamp  [depth][capacity]     int64 ns
+ *   sample [depth][3][capacity]  fp64 {x, y, yaw}, map coordinates
+ *   count  [capacity]            samples stored, at most depth
+ *   newest [capacity]            slot of the newest sample
+ *   held   [7][capacity]         fp64 {x, y, theta, v, vn, w, steer}: robot_pose_, robot_vel_ and
+ *                                robot_steering_wheel_angle_ of every robot
+ * 2 <= depth <= 64. Everything is 0 at enable: the reference leaves the three held members uninitialised until their
+ * first successful read, 0 is this project's rule. A second call with the same depth is a no-op, another depth is
+ * NMPC_ERR_ARG. nmpc_batch_input_state is the checkpoint view (each output may be NULL; every pointer is NULL and
+ * *depth 0 while the state is off; *stride = capacity). */
+int nmpc_batch_enable_input(nmpc_batch* b, int depth);
+int nmpc_batch_input_state(nmpc_batch* b, long long** stamp, double** sample, int** count, int** newest, double** held,
+                           int* depth, int* stride);
+
+/* The listener: one small launch, one lane per robot. For the robots [0, B) with mask[i] != 0 (mask [B] device, NULL:
+ * all) the sample (stamp_ns[i], sample[:, i]) goes into the slot after newest (slot 0 of an empty ring), newest moves
+ * there and count saturates at depth. A sample is dropped -- dropped[i] = 1, nothing of the robot changes -- when its
+ * stamp is <= the newest stored stamp or any of its three values is not finite; every other robot of [0, B) gets
+ * dropped[i] = 0 (dropped [B] device, or NULL). tf2 is not in the reference tree: this rule (stamps strictly increase,
+ * the oldest sample is overwritten) is the project's own, as the nearest-point search is.
+ * Argument errors: B out of range, stamp_ns or sample NULL, a NULL handle, no input state. */
+int nmpc_batch_push_samples(nmpc_batch* b, int B, const long long* stamp_ns, const double* sample /* [3][B] x, y, yaw */,
+                            const unsigned char* mask, unsigned char* dropped /* [B] or NULL */, void* stream);
+
+#define NMPC_NODE_EV_INPUT_INVALID (8) /* nmpc_batch_node_cycle, strict: the input data were invalid, -> Error */
+
+typedef struct nmpc_node_input {
+    long long now_ns;              /* ros::Time::now() of this cycle */
+    long long period_ns;           /* Duration(1.0 / control_freq): default 25000000 */
+    double transform_timeout;      /* s, default 0.1 (nmpc_nav_control.yaml:5) */
+    int pose_valid_overwritten;    /* default 1: getInputData:549-550 assigns valid_data twice, so the pose check is lost */
+    int strict;                    /* default 0, see the cycle */
+    double recentre_radius;        /* default +inf: never; finite: recentre in this launch */
+    const float* steer;            /* [B] measured steering angle (tric) or NULL = 0 */
+    const unsigned char* steer_ok; /* [B] or NULL = all ok: getSteeringWheelAngle's result */
+    unsigned char* valid;          /* [B] out or NULL */
+    float *pose, *vel, *steer_out; /* [3][B], [3][B], [B] out or NULL (handle-owned buffers then) */
+    unsigned char* moved;          /* [B] out or NULL: 1 where this launch gave the robot a new origin */
+} nmpc_node_input;
+int nmpc_node_input_default(nmpc_node_input* in); /* scalars as above, pointers NULL */
+
+/* The stage: one launch, one lane per robot. It runs for a robot whose mode is GOTO_POSE, FOLLOW_PATH or BREAK (mode is
+ * read only); for IDLE, ERROR or a value above 4 it skips the input steps, leaves held untouched and sets valid = 1.
+ * For a robot that runs:
+ *   sec(d)     = (double)floor_div(d, 1e9) + 1e-9 * (double)(d - floor_div * 1e9): ros::Duration::toSec.
+ *   lookup(t)  (the project's rule) fails when count == 0, t < the oldest stored stamp or t > the newest. A stored
+ *              stamp equal to t gives that sample. Otherwise, with a and b the stored neighbours, ta < t < tb, and
+ *              r = sec(t - ta) / sec(tb - ta): x = (1 - r) xa + r xb, y likewise, yaw = ya + r normAngRad(yb - ya).
+ *   pose       (getRobotPose) an empty ring: pose_ok = 0 and the held pose stays. Otherwise held.x, held.y are the
+ *              newest sample's and held.theta the hack of :414-423 on (held.theta, yaw), the same comparisons and the
+ *              two loops, each coded for at most two trips (one is all a yaw within [-pi, pi], tf2::getYaw's range,
+ *              can need, so no value can spin them); pose_ok = !(sec(now - stamp_newest) > transform_timeout). The
+ *              pose is written even when it is stale, as in the reference.
+ *   velocity   (getRobotVel) t2 = the newest stamp, t1 = t2 - period_ns, both looked up. A failed lookup, or
+ *              dt = sec(t2 - t1) with dt <= 0 || dt > transform_timeout, gives vel_ok = 0 and the velocity is held;
+ *              otherwise :456-476 in that operation order into held.v, vn, w.
+ *   steering   (tric handles) steer_ok[i] == 0: steer_valid = 0, the held value stays; else held.steer = steer[i].
+ *   valid      pose_valid_overwritten ? vel_ok : pose_ok && vel_ok; tric: &= steer_valid.
+ *   recentre   recentre_radius finite: nmpc_batch_recentre's decision and move on (held.x, held.y), for the robots that
+ *              ran the stage, in this launch (a frame table that is off is started, as nmpc_batch_recentre does); moved
+ *              as there. A non-finite radius reads nothing of the frame table but the origins.
+ * Outputs, for every robot of [0, B): pose = (float)(held.xy - origin_i) with the origin after any recentre ((0, 0)
+ * while the table is off) and (float)held.theta; vel and steer_out the fp32 roundings of the held values; goal_out =
+ * (float)(goal_map.xy - origin_i), (float)goal_map.theta when goal_map and goal_out are both given. No loop depends on
+ * the data (the ring is walked depth times by every lane), every read is instance-minor, and every fp64 product-sum is
+ * compiled without contraction, so x, y, theta and the ring are reproducible on the host bit for bit; the velocity
+ * goes through cos and sin and is reproducible to 1e-12.
+ * Out of scope: quaternion decoding (tf2::getYaw: the samples carry a yaw), the per-mode TF frame ids of
+ * mainCycle:520-528 (one map frame per robot, the caller's), the wheel-frame TF chain of getSteeringWheelAngle (the
+ * caller gives angle and ok flag) and the capsule ABI.
+ * Argument errors: B out of range, in NULL, mode NULL, a NULL handle, no input state. */
+int nmpc_batch_node_input(nmpc_batch* b, int B, const nmpc_node_input* in, const unsigned char* mode,
+                          const double* goal_map /* [3][B] or NULL */, float* goal_out /* [3][B] or NULL */, void* stream);
+
+/* The whole cycle: the stage, then nmpc_batch_node_tick (q NULL; nseg is read) or nmpc_batch_node_tick_queue (q given)
+ * on the stage's fp32 outputs, with those calls' launches and kernels, then the status rule in one small launch.
+ * Everything is queued on `stream`, no host synchronisation. goal_map [3][B] fp64 map coordinates or NULL (no robot in
+ * GOTO_POSE); in->pose, vel, steer_out, valid may be NULL (the handle's buffers carry the values to the tick). steer
+ * reaches the tick on tric handles only. Everything else as the tick's arguments.
+ *   strict = 0 (the node as written): getInputData sets Error, but the process* call of the same cycle still runs on
+ *     the held values (:519-529), so the tick runs as the mode says. Afterwards a robot with valid == 0 whose mode is
+ *     still GOTO_POSE or FOLLOW_PATH goes to ERROR (its remains to NaN); a robot the tick sent to IDLE or ERROR keeps
+ *     that. Event and command are the tick's.
+ *   strict = 1: an invalid robot does not tick: stop command, mode ERROR, event NMPC_NODE_EV_INPUT_INVALID, and its
+ *     resident rows (iterate, carried refs, warm flag, records, placement key, path window, path_u, reset) stay bit for
+ *     bit. (Its mode is set to ERROR before the gate and its event after the tick; the gate is unchanged.)
+ * Argument errors: the tick's, in NULL, and a handle without input state. The ticks compute what they computed, with
+ * the input state on or off. */
+int nmpc_batch_node_cycle(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_queue* q /* NULL: plain tick */,
+                          const nmpc_node_input* in, unsigned char* mode, const double* goal_map,
+                          const nmpc_path_segment* segs, int seg_stride, const int* nseg /* read when q is NULL */,
+                          double* path_u, unsigned char* reset, unsigned char* event, double* err, float* traj_out,
+                          int* n_solved, float* cmd, float* u0, int* status, int* qp_iter, float* qp_res, void* stream);
 
 /* Kernel variant: NMPC_KERNEL_TEAM (16-lane team per robot, DPP row exchange) is the only one; any other value
  * returns NMPC_ERR_UNSUPPORTED. (The round-1 one-lane-per-robot kernel was removed: its fp32 factor is not

@@ -71,6 +71,15 @@ class PathQueueStruct(ctypes.Structure):
                 ("remains", c_void_p)]
 
 
+class NodeInputStruct(ctypes.Structure):
+    """Mirror of nmpc_node_input (include/nmpc_amd/nmpc_batch.h)."""
+    _fields_ = [("now_ns", ctypes.c_longlong), ("period_ns", ctypes.c_longlong),
+                ("transform_timeout", ctypes.c_double), ("pose_valid_overwritten", ctypes.c_int),
+                ("strict", ctypes.c_int), ("recentre_radius", ctypes.c_double), ("steer", c_void_p),
+                ("steer_ok", c_void_p), ("valid", c_void_p), ("pose", c_void_p), ("vel", c_void_p),
+                ("steer_out", c_void_p), ("moved", c_void_p)]
+
+
 class RobotParamsStruct(ctypes.Structure):
     """Mirror of nmpc_robot_params (include/nmpc_amd/nmpc_batch.h): device pointers [n][B], None = rows untouched."""
     _fields_ = [("lbx", c_void_p), ("ubx", c_void_p), ("lbu", c_void_p), ("ubu", c_void_p), ("W", c_void_p),
@@ -88,6 +97,7 @@ NODE_IDLE, NODE_GOTO_POSE, NODE_FOLLOW_PATH, NODE_BREAK, NODE_ERROR = 0, 1, 2, 3
 (NODE_EV_NONE, NODE_EV_SOLVED, NODE_EV_ARRIVED, NODE_EV_GOAL_TOO_FAR, NODE_EV_OFF_PATH, NODE_EV_SOLVE_FAILED,
  NODE_EV_BREAK) = range(7)
 NODE_EV_NEXT_PART = 7  # nmpc_batch_node_tick_queue only
+NODE_EV_INPUT_INVALID = 8  # nmpc_batch_node_cycle with strict = 1 only
 
 
 class CodegenDesc(ctypes.Structure):
@@ -124,6 +134,8 @@ BATCH_SYMBOLS = [
     "nmpc_batch_set_robot_model", "nmpc_batch_robot_model", "nmpc_batch_clear_robot_model",
     "nmpc_batch_set_robot_frame", "nmpc_batch_recentre", "nmpc_batch_to_frame", "nmpc_batch_from_frame",
     "nmpc_batch_robot_frame", "nmpc_batch_clear_robot_frame",
+    "nmpc_batch_enable_input", "nmpc_batch_input_state", "nmpc_batch_push_samples", "nmpc_node_input_default",
+    "nmpc_batch_node_input", "nmpc_batch_node_cycle",
     "nmpc_fleet_sim_step", "nmpc_fleet_sim_step_renew", "nmpc_fleet_hash",
     "nmpc_last_error", "nmpc_version", "nmpc_path_discretize", "nmpc_path_nearest", "nmpc_codegen_default", "nmpc_capsule_new",
     "nmpc_capsule_delete", "nmpc_capsule_create", "nmpc_capsule_reset", "nmpc_capsule_update_params",
@@ -183,6 +195,14 @@ def lib():
     L.nmpc_batch_node_tick_queue.argtypes = [vp, i, ctypes.POINTER(NodeParamsStruct), ctypes.POINTER(PathQueueStruct),
                                              vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                              vp]
+    NI = ctypes.POINTER(NodeInputStruct)
+    L.nmpc_batch_enable_input.argtypes = [vp, i]
+    L.nmpc_batch_input_state.argtypes = [vp] + [ctypes.POINTER(vp)] * 5 + [c_int_p, c_int_p]
+    L.nmpc_batch_push_samples.argtypes = [vp, i, vp, vp, vp, vp, vp]
+    L.nmpc_node_input_default.argtypes = [NI]
+    L.nmpc_batch_node_input.argtypes = [vp, i, NI, vp, vp, vp, vp]
+    L.nmpc_batch_node_cycle.argtypes = [vp, i, ctypes.POINTER(NodeParamsStruct), ctypes.POINTER(PathQueueStruct), NI,
+                                        vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.nmpc_batch_set_kernel.argtypes = [vp, i]
     L.nmpc_batch_set_schedule.argtypes = [vp, i]
     L.nmpc_batch_state.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), c_int_p]

@@ -9,8 +9,8 @@ import ctypes
 import torch
 
 from ._lib import (KERNELS, MODEL_IDS, PLAN_MODES, REC_LAYOUTS, SCHEDULES, FleetRenew, FleetStats, LaunchPlan,
-                   ModelParams, NodeParamsStruct, RobotParamsStruct, StageBoundsStruct, check, default_params, lib,
-                   model_dims)
+                   ModelParams, NodeInputStruct, NodeParamsStruct, RobotParamsStruct, StageBoundsStruct, check,
+                   default_params, lib, model_dims)
 
 
 def _ptr(t, dtype=None, shape=None, name="argument"):
@@ -64,6 +64,51 @@ class NodeParams:
         if k != "c" and k in dict(NodeParamsStruct._fields_):
             return getattr(self.c, k)
         raise AttributeError(k)
+
+
+class NodeInput:
+    """nmpc_node_input (include/nmpc_amd/nmpc_batch.h): the arguments of the node's input stage. ``default()`` is the
+    shipped configuration (40 Hz, transform_timeout 0.1 s, the pose check lost as in getInputData, lenient, no
+    recentre); keyword arguments override fields. The scalar fields are numbers; steer (float32 [B]), steer_ok, valid,
+    moved (uint8 [B]), pose, vel (float32 [3][B]) and steer_out (float32 [B]) are device tensors or None, which this
+    object keeps alive."""
+
+    _SHAPES = dict(steer=(F32, 1), steer_ok=(U8, 1), valid=(torch.uint8, 1), pose=(F32, 3), vel=(F32, 3),
+                   steer_out=(F32, 1), moved=(torch.uint8, 1))
+
+    def __init__(self, **fields):
+        self.c = NodeInputStruct()
+        check(lib().nmpc_node_input_default(ctypes.byref(self.c)), "nmpc_node_input_default")
+        self.tensors = {}
+        for k, v in fields.items():
+            setattr(self, k, v)
+
+    @classmethod
+    def default(cls, **fields):
+        return cls(**fields)
+
+    def __setattr__(self, k, v):
+        if k in ("c", "tensors"):
+            object.__setattr__(self, k, v)
+        elif k in self._SHAPES:
+            self.tensors[k] = v
+        elif k in dict(NodeInputStruct._fields_):
+            setattr(self.c, k, v)
+        else:
+            raise AttributeError(f"nmpc_node_input has no field {k}")
+
+    def __getattr__(self, k):
+        if k in NodeInput._SHAPES:
+            return self.tensors.get(k)
+        if k != "c" and k in dict(NodeInputStruct._fields_):
+            return getattr(self.c, k)
+        raise AttributeError(k)
+
+    def struct(self, B):
+        """the C struct with the tensors' device pointers, each checked against the shape a call of B robots reads"""
+        for k, (dtype, rows) in self._SHAPES.items():
+            setattr(self.c, k, _ptr(self.tensors.get(k), dtype, (B,) if rows == 1 else (rows, B), k))
+        return self.c
 
 
 class BatchSolver:
@@ -332,12 +377,15 @@ class BatchSolver:
         """Device copies of everything a solve reads from the handle: iterate, carried refs, warm start (five
         tensors), then the per-robot table as a tensor when it is on, then the stage table as
         {"stage_bounds": bytes}, the model table as {"robot_model": tensor} and the frame table as {"robot_frame":
-        tensor} when they are on."""
+        tensor} when they are on, then the node's input state as {"node_input": {...}} when it is enabled."""
         saved = [v.to_tensor() for v in self.state() + self.warm_state()]
         for name, view, _, _ in self._tables():
             v = view()
             if v is not None:
                 saved.append(v.to_tensor() if name is None else {name: v.to_tensor()})
+        ist = self.input_state()
+        if ist is not None:  # the node's input state: {"node_input": {"depth": int, "stamp": tensor, ...}}
+            saved.append({"node_input": {k: (v if k == "depth" else v.to_tensor()) for k, v in ist.items()}})
         return saved
 
     def restore_state(self, saved):
@@ -348,6 +396,16 @@ class BatchSolver:
         have = {}
         for e in saved[5:]:
             have.update(e if isinstance(e, dict) else {None: e})
+        # the input state as the checkpoint has it; a checkpoint without one leaves a state that is on as enable_input
+        # does, all 0
+        inp, ist = have.pop("node_input", None), self.input_state()
+        if inp is not None:
+            self.enable_input(inp["depth"])
+            ist = self.input_state()
+        if ist is not None:
+            for k, v in ist.items():
+                if k != "depth":
+                    v.copy_from(inp[k] if inp is not None else torch.zeros(v.shape, dtype=v.dtype))
         for name, _, load, clear in reversed(self._tables()):
             if name in have:
                 load(have[name].to(self.device))
@@ -537,6 +595,72 @@ class BatchSolver:
             _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"), _ptr(n_solved, I32, (1,), "n_solved"),
             *self._outputs(B, cmd, u0, status, qp_iter, qp_res, stream)), "nmpc_batch_node_tick_queue")
 
+    def enable_input(self, depth):
+        """Allocate the node's input state (nmpc_batch_enable_input): a ring of `depth` localisation samples per robot
+        (2 <= depth <= 64) and the held pose, velocity and steering angle, all 0. The same depth again is a no-op."""
+        check(lib().nmpc_batch_enable_input(self._h, int(depth)), "nmpc_batch_enable_input")
+
+    def input_state(self):
+        """Views of the input state (nmpc_batch_input_state), or None while it is off: dict with depth, stamp int64
+        [depth][cap], sample float64 [depth*3][cap] (slot-major, then x, y, yaw), count and newest int32 [1][cap], held
+        float64 [7][cap] (x, y, theta, v, vn, w, steer)."""
+        ptrs = [ctypes.c_void_p() for _ in range(5)]
+        depth, stride = ctypes.c_int(), ctypes.c_int()
+        check(lib().nmpc_batch_input_state(self._h, *[ctypes.byref(p) for p in ptrs], ctypes.byref(depth),
+                                           ctypes.byref(stride)), "nmpc_batch_input_state")
+        if not depth.value:
+            return None
+        D, S = depth.value, stride.value
+        shapes = (("stamp", (D, S), I64), ("sample", (3 * D, S), F64), ("count", (1, S), I32), ("newest", (1, S), I32),
+                  ("held", (7, S), F64))
+        out = {k: _DeviceView(p.value, shape, self.device, dt) for p, (k, shape, dt) in zip(ptrs, shapes)}
+        out["depth"] = D
+        return out
+
+    def push_samples(self, stamp_ns, sample, mask=None, dropped=None, stream=None):
+        """The listener (nmpc_batch_push_samples): stamp_ns int64 [B] nanoseconds, sample float64 [3][B] {x, y, yaw} in
+        map coordinates; mask uint8 [B] selects the robots (None: all). A sample whose stamp is not after the robot's
+        newest one, or that is not finite, is dropped: dropped uint8 [B] (optional) receives 1 there."""
+        B = self._batch_of(sample)
+        check(lib().nmpc_batch_push_samples(self._h, B, _ptr(stamp_ns, I64, (B,), "stamp_ns"),
+                                            _ptr(sample, F64, (3, B), "sample"), _ptr(mask, U8, (B,), "mask"),
+                                            _ptr(dropped, torch.uint8, (B,), "dropped"), _stream(stream)),
+              "nmpc_batch_push_samples")
+
+    def node_input(self, node_input, mode, goal_map=None, goal_out=None, stream=None):
+        """The node's input stage, getInputData (nmpc_batch_node_input), for the robots of mode uint8 [B]: pose with
+        the heading hack, finite-difference velocity and data ages from the sample rings into the held values, the
+        optional recentre, and the float32 frame values of node_input.pose / vel / steer_out / valid (a NodeInput);
+        goal_map float64 [3][B] becomes goal_out float32 [3][B] in the robots' frames."""
+        B = self._batch_of(mode, 0)
+        check(lib().nmpc_batch_node_input(self._h, B, ctypes.byref(node_input.struct(B)),
+                                          _ptr(mode, torch.uint8, (B,), "mode"), _ptr(goal_map, F64, (3, B), "goal_map"),
+                                          _ptr(goal_out, F32, (3, B), "goal_out"), _stream(stream)),
+              "nmpc_batch_node_input")
+
+    def node_cycle(self, node_params, node_input, mode, goal_map=None, segs=None, nseg=None, path_u=None, queue=None,
+                   reset=None, event=None, err=None, traj_out=None, n_solved=None, cmd=None, u0=None, status=None,
+                   qp_iter=None, qp_res=None, stream=None):
+        """The whole control cycle in one call (nmpc_batch_node_cycle): node_input's stage, then node_tick (or, with
+        queue, a nmpc_nav_control_amd.path.PathQueue, node_tick_queue) on the stage's outputs, then the status rule
+        for the robots whose input data were invalid (node_input.strict). goal_map float64 [3][B] in map coordinates;
+        everything else as node_tick / node_tick_queue."""
+        B = self._batch_of(mode, 0)
+        if queue is not None:
+            if queue.B != B:
+                raise ValueError(f"queue: built for {queue.B} robots, the cycle has {B}")
+            segs, path_u, stride, q = queue.segs, queue.path_u, queue.S, ctypes.byref(queue.struct())
+        else:
+            stride, q = (_segs_stride(segs, B) if segs is not None else 1), None
+        check(lib().nmpc_batch_node_cycle(
+            self._h, B, ctypes.byref(node_params.c), q, ctypes.byref(node_input.struct(B)),
+            _ptr(mode, torch.uint8, (B,), "mode"), _ptr(goal_map, F64, (3, B), "goal_map"),
+            _ptr(segs, torch.float64, None, "segs"), stride, _ptr(nseg, I32, (B,), "nseg"),
+            _ptr(path_u, torch.float64, (B,), "path_u"), _ptr(reset, torch.uint8, (B,), "reset"),
+            _ptr(event, torch.uint8, (B,), "event"), _ptr(err, torch.float64, (2, B), "err"),
+            _ptr(traj_out, F32, (self.N + 1, 3, B), "traj_out"), _ptr(n_solved, I32, (1,), "n_solved"),
+            *self._outputs(B, cmd, u0, status, qp_iter, qp_res, stream)), "nmpc_batch_node_cycle")
+
     def fleet_sim_step(self, path, s, pose, vel, steer, u0, status, traj, traj_len, advance=True, stream=None):
         B = self._batch_of(pose)
         check(lib().nmpc_fleet_sim_step(
@@ -618,4 +742,4 @@ def _hip():
     return _hip_lib
 
 
-__all__ = ["BatchSolver", "ModelParams", "NodeParams", "default_params"]
+__all__ = ["BatchSolver", "ModelParams", "NodeInput", "NodeParams", "default_params"]

@@ -80,6 +80,12 @@ struct nmpc_batch {
     DevTable rparams, sbounds, rmodel, rframe;
     RpRows rp{};
     int np = 0;
+    // the node's input state (nmpc_batch_enable_input; in_depth 0: off): every robot's sample ring and held values,
+    // and the buffers that carry the stage's outputs to the tick when the caller keeps none (pose, vel, goal [3][B],
+    // steer, valid [B], each allocated for the capacity)
+    NodeInputState in_st{};
+    float *in_pose = nullptr, *in_vel = nullptr, *in_goal = nullptr, *in_steer = nullptr;
+    unsigned char* in_valid = nullptr;
 };
 
 namespace {
@@ -691,6 +697,10 @@ int nmpc_batch_destroy(nmpc_batch* b)
     (void)hipFree(b->node_n);
     (void)hipFree(b->node_status);
     for (const DevTable* t : {&b->rparams, &b->sbounds, &b->rmodel, &b->rframe}) (void)hipFree(t->p);
+    for (void* p : {(void*)b->in_st.stamp, (void*)b->in_st.sample, (void*)b->in_st.count, (void*)b->in_st.newest,
+                    (void*)b->in_st.held, (void*)b->in_pose, (void*)b->in_vel, (void*)b->in_goal, (void*)b->in_steer,
+                    (void*)b->in_valid})
+        (void)hipFree(p);
     delete b;
     return NMPC_OK;
 }
@@ -909,14 +919,12 @@ int nmpc_path_queue_default(nmpc_path_queue* q)
 
 namespace {
 
-// nmpc_batch_node_tick (q == nullptr) and nmpc_batch_node_tick_queue (q given, nseg unused)
-int node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_queue* q, unsigned char* mode,
-              const float* pose, const float* vel, const float* steer, const float* goal,
-              const nmpc_path_segment* segs, int seg_stride, const int* nseg, double* path_u, unsigned char* reset,
-              unsigned char* event, double* err, float* traj_out, int* n_solved, float* cmd, float* u0, int* status,
-              int* qp_iter, float* qp_res, void* stream)
+// the argument checks of a node tick, those that need no handle first; *go: there is work (B > 0)
+int node_tick_check(const nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_queue* q,
+                    const unsigned char* mode, const float* pose, const float* vel, const nmpc_path_segment* segs,
+                    int seg_stride, const int* nseg, const double* path_u, bool* go)
 {
-    // the checks that need no handle come first
+    *go = false;
     if (!np) return set_err(NMPC_ERR_ARG, "node params is NULL");
     if (q) {
         if (segs && !(q->npart && q->head && q->tail))
@@ -935,6 +943,21 @@ int node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_
     const bool paths = segs && (q || nseg) && path_u;
     if (paths && node_gate_lds_bytes(b->prm.N) > 65536)
         return set_err(NMPC_ERR_UNSUPPORTED, "horizon too long for the gate's path march");
+    *go = true;
+    return NMPC_OK;
+}
+
+// nmpc_batch_node_tick (q == nullptr) and nmpc_batch_node_tick_queue (q given, nseg unused)
+int node_tick(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_queue* q, unsigned char* mode,
+              const float* pose, const float* vel, const float* steer, const float* goal,
+              const nmpc_path_segment* segs, int seg_stride, const int* nseg, double* path_u, unsigned char* reset,
+              unsigned char* event, double* err, float* traj_out, int* n_solved, float* cmd, float* u0, int* status,
+              int* qp_iter, float* qp_res, void* stream)
+{
+    bool go = false;
+    if (const int rc = node_tick_check(b, B, np, q, mode, pose, vel, segs, seg_stride, nseg, path_u, &go)) return rc;
+    if (!go) return NMPC_OK;
+    const bool paths = segs && (q || nseg) && path_u;
     hipStream_t s = (hipStream_t)stream;
     if (!b->node_traj) {
         const size_t S = (size_t)b->capacity;
@@ -1016,6 +1039,150 @@ int nmpc_batch_node_tick_queue(nmpc_batch* b, int B, const nmpc_node_params* np,
     if (!q) return set_err(NMPC_ERR_ARG, "path queue is NULL");
     return node_tick(b, B, np, q, mode, pose, vel, steer, goal, segs, seg_stride, nullptr, path_u, reset, event, err,
                      traj_out, n_solved, cmd, u0, status, qp_iter, qp_res, stream);
+}
+
+int nmpc_batch_enable_input(nmpc_batch* b, int depth)
+{
+    if (depth < 2 || depth > 64) return set_err(NMPC_ERR_ARG, "input depth out of range [2, 64]");
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (b->in_st.depth) {
+        if (b->in_st.depth == depth) return NMPC_OK;
+        return set_err(NMPC_ERR_ARG, "input state is enabled with another depth");
+    }
+    const size_t S = (size_t)b->capacity, D = (size_t)depth;
+    NodeInputState st{};
+    st.cap = b->capacity;
+    st.depth = depth;
+    // everything starts as 0: empty rings, and held values where the reference has uninitialised members
+    auto zeroed = [&](auto** p, size_t n) {
+        const size_t bytes = sizeof(**p) * n;
+        hipError_t e = hipMalloc(p, bytes);
+        return e != hipSuccess ? e : hipMemset(*p, 0, bytes);
+    };
+    hipError_t e;
+    if ((e = zeroed(&st.stamp, D * S)) != hipSuccess || (e = zeroed(&st.sample, D * 3 * S)) != hipSuccess ||
+        (e = zeroed(&st.count, S)) != hipSuccess || (e = zeroed(&st.newest, S)) != hipSuccess ||
+        (e = zeroed(&st.held, 7 * S)) != hipSuccess || (e = zeroed(&b->in_pose, 3 * S)) != hipSuccess ||
+        (e = zeroed(&b->in_vel, 3 * S)) != hipSuccess || (e = zeroed(&b->in_goal, 3 * S)) != hipSuccess ||
+        (e = zeroed(&b->in_steer, S)) != hipSuccess || (e = zeroed(&b->in_valid, S)) != hipSuccess ||
+        (e = hipStreamSynchronize(nullptr)) != hipSuccess) {
+        for (void* p : {(void*)st.stamp, (void*)st.sample, (void*)st.count, (void*)st.newest, (void*)st.held,
+                        (void*)b->in_pose, (void*)b->in_vel, (void*)b->in_goal, (void*)b->in_steer, (void*)b->in_valid})
+            (void)hipFree(p);
+        b->in_pose = b->in_vel = b->in_goal = b->in_steer = nullptr;
+        b->in_valid = nullptr;
+        return hip_err(e, "hipMalloc");
+    }
+    b->in_st = st;
+    return NMPC_OK;
+}
+
+int nmpc_batch_input_state(nmpc_batch* b, long long** stamp, double** sample, int** count, int** newest, double** held,
+                           int* depth, int* stride)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (stamp) *stamp = b->in_st.stamp;
+    if (sample) *sample = b->in_st.sample;
+    if (count) *count = b->in_st.count;
+    if (newest) *newest = b->in_st.newest;
+    if (held) *held = b->in_st.held;
+    if (depth) *depth = b->in_st.depth;
+    if (stride) *stride = b->capacity;
+    return NMPC_OK;
+}
+
+int nmpc_batch_push_samples(nmpc_batch* b, int B, const long long* stamp_ns, const double* sample,
+                            const unsigned char* mask, unsigned char* dropped, void* stream)
+{
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!stamp_ns || !sample) return set_err(NMPC_ERR_ARG, "push_samples: stamp_ns and sample are required");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (!b->in_st.depth) return set_err(NMPC_ERR_ARG, "the input state is not enabled (nmpc_batch_enable_input)");
+    return hip_err(launch_push_samples(b->in_st, B, stamp_ns, sample, mask, dropped, (hipStream_t)stream),
+                   "push_samples launch");
+}
+
+int nmpc_node_input_default(nmpc_node_input* in)
+{
+    if (!in) return set_err(NMPC_ERR_ARG, "node input is NULL");
+    std::memset(in, 0, sizeof(*in));
+    in->period_ns = 25000000;         // Duration(1.0 / control_freq), nmpc_nav_control.yaml:4
+    in->transform_timeout = 0.1;      // :5
+    in->pose_valid_overwritten = 1;   // NMPCNavControlROS.cpp:549-550
+    in->recentre_radius = INFINITY;
+    return NMPC_OK;
+}
+
+namespace {
+// The stage's launch. mode_rw: the cycle's mode array under strict, else nullptr; goal_out may be the handle's buffer.
+// *res: the stage's arguments with the handle's buffers where the caller keeps none
+int node_input(nmpc_batch* b, int B, const nmpc_node_input* in, const unsigned char* mode, unsigned char* mode_rw,
+               const double* goal_map, float* goal_out, hipStream_t s, nmpc_node_input* res)
+{
+    NodeInputArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.st = b->in_st;
+    a.B = B;
+    a.tric = b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0;
+    a.in = *in;
+    if (!a.in.valid) a.in.valid = b->in_valid;
+    if (!a.in.pose) a.in.pose = b->in_pose;
+    if (!a.in.vel) a.in.vel = b->in_vel;
+    if (!a.in.steer_out) a.in.steer_out = b->in_steer;
+    a.mode = mode;
+    a.mode_rw = mode_rw;
+    a.goal_map = goal_map;
+    a.goal_out = goal_out;
+    if (std::isfinite(in->recentre_radius))  // a frame table that is off is started, as nmpc_batch_recentre does
+        if (const int rc = rf_table(b, s)) return rc;
+    a.fr = b->rframe.view64();
+    a.xbar = b->xbar;
+    a.N = b->prm.N;
+    a.nx = b->nx;
+    if (res) *res = a.in;
+    return hip_err(launch_node_input(a, s), "node_input launch");
+}
+}  // namespace
+
+int nmpc_batch_node_input(nmpc_batch* b, int B, const nmpc_node_input* in, const unsigned char* mode,
+                          const double* goal_map, float* goal_out, void* stream)
+{
+    const TraceRange trace("nmpc_batch_node_input");
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!in) return set_err(NMPC_ERR_ARG, "node input is NULL");
+    if (!mode) return set_err(NMPC_ERR_ARG, "mode is required");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (!b->in_st.depth) return set_err(NMPC_ERR_ARG, "the input state is not enabled (nmpc_batch_enable_input)");
+    if (B == 0) return NMPC_OK;
+    return node_input(b, B, in, mode, nullptr, goal_map, goal_out, (hipStream_t)stream, nullptr);
+}
+
+int nmpc_batch_node_cycle(nmpc_batch* b, int B, const nmpc_node_params* np, const nmpc_path_queue* q,
+                          const nmpc_node_input* in, unsigned char* mode, const double* goal_map,
+                          const nmpc_path_segment* segs, int seg_stride, const int* nseg, double* path_u,
+                          unsigned char* reset, unsigned char* event, double* err, float* traj_out, int* n_solved,
+                          float* cmd, float* u0, int* status, int* qp_iter, float* qp_res, void* stream)
+{
+    const TraceRange trace("nmpc_batch_node_cycle");
+    if (!in) return set_err(NMPC_ERR_ARG, "node input is NULL");
+    // every check of the tick before the stage changes anything (pose and vel are the stage's: never NULL)
+    bool go = false;
+    const float some = 0.0f;
+    if (const int rc = node_tick_check(b, B, np, q, mode, &some, &some, segs, seg_stride, q ? nullptr : nseg, path_u, &go))
+        return rc;
+    if (!b->in_st.depth) return set_err(NMPC_ERR_ARG, "the input state is not enabled (nmpc_batch_enable_input)");
+    if (!go) return NMPC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    nmpc_node_input r;
+    float* const goal = goal_map ? b->in_goal : nullptr;
+    int rc = node_input(b, B, in, mode, in->strict ? mode : nullptr, goal_map, goal, s, &r);
+    if (rc) return rc;
+    const float* const steer = b->prm.model == NMPC_MODEL_TRIC3AMR ? r.steer_out : nullptr;
+    rc = node_tick(b, B, np, q, mode, r.pose, r.vel, steer, goal, segs, seg_stride, q ? nullptr : nseg, path_u, reset,
+                   event, err, traj_out, n_solved, cmd, u0, status, qp_iter, qp_res, stream);
+    if (rc) return rc;
+    return hip_err(launch_cycle_status(B, r.valid, in->strict ? 1 : 0, mode, event, q ? q->remains : nullptr, s),
+                   "cycle_status launch");
 }
 
 int nmpc_batch_set_kernel(nmpc_batch* b, int kernel)

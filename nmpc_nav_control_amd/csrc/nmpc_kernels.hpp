@@ -268,4 +268,34 @@ hipError_t launch_node_finish(int B, const unsigned char* active, const int* sta
                               unsigned char* mode, unsigned char* event, unsigned char* reset, int* n_solved,
                               double* remains, hipStream_t stream);
 
+// The node's input stage (node_input.hip, nmpc_batch_node_input): the handle's sample rings and held values, all
+// instance-minor with stride cap (ring: stamp [depth][cap], sample [depth][3][cap], count / newest [cap]; held [7][cap])
+struct NodeInputState {
+    int cap, depth;
+    long long* stamp;
+    double* sample;
+    int* count;
+    int* newest;
+    double* held;
+};
+hipError_t launch_push_samples(const NodeInputState& st, int B, const long long* stamp_ns, const double* sample,
+                               const unsigned char* mask, unsigned char* dropped, hipStream_t stream);
+struct NodeInputArgs {
+    NodeInputState st;
+    int B, tric;
+    nmpc_node_input in;         // scalars and the caller's arrays; valid, pose, vel, steer_out resolved (never NULL)
+    const unsigned char* mode;  // [B]
+    unsigned char* mode_rw;     // the cycle under strict: an invalid robot's mode becomes NMPC_NODE_ERROR; else nullptr
+    const double* goal_map;     // [3][B] or nullptr
+    float* goal_out;
+    double* fr;  // the frame table [2][cap] or nullptr (off: origin zero); written only with a finite recentre_radius
+    float* xbar;  // the resident iterate, moved with a robot's origin
+    int N, nx;
+};
+hipError_t launch_node_input(const NodeInputArgs& a, hipStream_t stream);
+// the status rule of nmpc_batch_node_cycle after the tick, for the robots with valid[i] == 0: strict: event
+// INPUT_INVALID; else a mode that is still GOTO_POSE or FOLLOW_PATH becomes ERROR (remains, the queue's, NaN)
+hipError_t launch_cycle_status(int B, const unsigned char* valid, int strict, unsigned char* mode, unsigned char* event,
+                               double* remains, hipStream_t stream);
+
 }  // namespace nmpc

@@ -13,6 +13,7 @@
 // Every writer is one elementwise launch on the caller's stream: x over robots in blocks of 256, thread i of a row, of
 // a (stage, row) or of a stage writes robot i (a row-major row's stores are coalesced), every index is checked against
 // B <= capacity, and nothing is read back or checked on the host.
+#include "frame_move.hpp"
 #include "nmpc_kernels.hpp"
 
 namespace nmpc {
@@ -172,8 +173,7 @@ __global__ void k_frame_set(double* fr, int cap, int B, float* xbar, int N, int 
     double nx_o = 0.0, ny_o = 0.0;
     if (pose_map) {
         const double x = pose_map[i], y = pose_map[(size_t)B + i];
-        // (false on a NaN position or radius)
-        go = go && (fabs(x - ox) > radius || fabs(y - oy) > radius) && isfinite(x) && isfinite(y);
+        go = go && frame_recentre_go(x, y, ox, oy, radius);
         nx_o = rint(x);
         ny_o = rint(y);
         if (moved) moved[i] = go ? 1 : 0;
@@ -182,14 +182,7 @@ __global__ void k_frame_set(double* fr, int cap, int B, float* xbar, int N, int 
         ny_o = origin[(size_t)B + i];
     }
     if (!go) return;
-    fr[i] = nx_o;
-    fr[(size_t)cap + i] = ny_o;
-    const double dx = ox - nx_o, dy = oy - ny_o;
-    for (int k = 0; k <= N; k++) {
-        float* const x = xbar + ((size_t)k * nx) * cap + i;
-        x[0] = (float)((double)x[0] + dx);
-        x[cap] = (float)((double)x[cap] + dy);
-    }
+    frame_move(fr, cap, i, xbar, N, nx, ox, oy, nx_o, ny_o);
 }
 
 // element e of an array [n][c][B]: robot e % B, component (e / B) % c

@@ -22,9 +22,15 @@ nmpc_batch_node_tick on the same paths (the cost of the queue), and the queue ti
 path as the first part of a forward / reverse / forward set, so that the window logic has parts to look at). Five
 interleaved timed windows of each after a warm-up, median and spread; one JSON line per B.
 
+With --cycle: nmpc_batch_node_cycle (the input stage, the node tick and the status rule in one call, from fp64 map
+samples) on --node's mixed fleet, against nmpc_batch_node_tick on a twin handle fed the inputs the stage emitted
+(prepared beforehand: what a caller with a host-side getInputData hands over), and the stage's and the listener's
+launches alone. Three interleaved rounds of each, the median; one JSON line per (B, fraction).
+
 Poses of --nearest and --tick: the path points at the seeded nearest_u, displaced by a seeded offset of up to 0.1 m.
 
-usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick | --node | --mission]
+usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick | --node | --mission |
+                                                                                     --cycle]
 """
 import argparse
 import json
@@ -125,7 +131,10 @@ def main(argv=None):
     ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--node", action="store_true")
     ap.add_argument("--mission", action="store_true")
+    ap.add_argument("--cycle", action="store_true")
     a = ap.parse_args(argv)
+    if a.cycle:
+        return cycle_bench(a)
     if a.mission:
         return mission_bench(a)
     if a.node:
@@ -286,6 +295,87 @@ def node_bench(a):
                             active=int((small["st"] != 0).sum())),
                 form_B="%s w%d" % (plan_b["kernel"], plan_b["waves_per_robot"]),
                 form_active="%s w%d" % (plan_k["kernel"], plan_k["waves_per_robot"]))), flush=True)
+
+
+def cycle_bench(a):
+    """node_cycle against node_tick on host-prepared inputs (see the module docstring). Both handles run warm-started
+    ticks on fixed samples with path_u fed back, as --node does; the rings (depth 4) hold two samples per robot one
+    period apart, so every active robot's pose and velocity are valid."""
+    from nmpc_nav_control_amd._lib import NODE_FOLLOW_PATH, NODE_GOTO_POSE
+    from nmpc_nav_control_amd.batch import BatchSolver, NodeInput, NodeParams
+    dev = torch.device("cuda:0")
+    N = a.num_poses - 1
+    npar = NodeParams.default()
+    stream = torch.cuda.current_stream()
+    i32, f64, now, period = torch.int32, torch.float64, 1700000000000000000, 25000000
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    for B in (4096, 1024):
+        segs, nseg, nu = seeded_paths(B)
+        pose = seeded_poses(segs, nseg, nu).astype(np.float64)
+        rng = np.random.default_rng(B)
+        ang, r = rng.uniform(-math.pi, math.pi, B), rng.uniform(0.3, 1.0, B)
+        goal = np.stack([pose[0] + r * np.cos(ang), pose[1] + r * np.sin(ang), pose[2] + rng.uniform(0.2, 1.0, B)])
+        perm = rng.permutation(B)
+        for frac in (1.0, 0.5, 0.25):
+            k = int(B * frac)
+            act = np.sort(perm[:k])
+            mode = np.zeros(B, np.uint8)
+            mode[act[0::2]] = NODE_FOLLOW_PATH
+            mode[act[1::2]] = NODE_GOTO_POSE
+
+            def handle():
+                return dict(solver=BatchSolver("diff", N, B, device=dev), S=t(segs), NS=t(nseg), M=t(mode),
+                            U=torch.zeros(B, dtype=f64, device=dev), u0=torch.zeros(2, B, device=dev),
+                            st=torch.zeros(B, dtype=i32, device=dev))
+
+            cyc, tick = handle(), handle()
+            stamp, smp = t(np.full(B, now - 2000000, np.int64)), t(pose)
+            s = cyc["solver"]
+            s.enable_input(4)
+            s.push_samples(stamp - period, smp)
+            s.push_samples(stamp, smp)
+            buf = dict(pose=torch.zeros(3, B, device=dev), vel=torch.zeros(3, B, device=dev),
+                       valid=torch.zeros(B, dtype=torch.uint8, device=dev))
+            nin, G = NodeInput.default(now_ns=now, **buf), t(goal)
+            gout = torch.zeros(3, B, device=dev)
+            nsolved = torch.zeros(1, dtype=i32, device=dev)
+
+            def stage_step():
+                s.node_input(nin, cyc["M"], goal_map=G, goal_out=gout)
+
+            def push_step():  # (the same stamp again: every sample is dropped, after the same reads)
+                s.push_samples(stamp, smp)
+
+            def cycle_step():
+                d = cyc
+                s.node_cycle(npar, nin, d["M"], goal_map=G, segs=d["S"], nseg=d["NS"], path_u=d["U"],
+                             n_solved=nsolved, u0=d["u0"], status=d["st"])
+
+            stage_step()  # the host-prepared inputs of the twin: what the stage emits
+            torch.cuda.synchronize()
+            P, V, G32 = buf["pose"].clone(), buf["vel"].clone(), gout.clone()
+
+            def tick_step():
+                d = tick
+                d["solver"].node_tick(npar, d["M"], P, V, goal=G32, segs=d["S"], nseg=d["NS"], path_u=d["U"],
+                                      u0=d["u0"], status=d["st"])
+
+            steps = {"node_cycle": cycle_step, "node_tick": tick_step, "stage": stage_step, "push": push_step}
+            ms = {k_: [] for k_ in steps}
+            for _ in range(3):
+                for k_, fn in steps.items():
+                    ms[k_].append(timed(fn, a.iters, stream))
+            med = {k_: sorted(v)[1] for k_, v in ms.items()}
+            same = all(torch.equal(cyc[k_], tick[k_]) for k_ in ("u0", "st", "M", "U"))
+            print(json.dumps(dict(
+                metric="node cycle ms (diff N=%d)" % N, B=B, active=k, n_solved=int(nsolved.cpu()),
+                node_cycle_ms=round(med["node_cycle"], 4), node_tick_ms=round(med["node_tick"], 4),
+                stage_ms=round(med["stage"], 4), push_ms=round(med["push"], 4),
+                cycle_minus_tick_ms=round(med["node_cycle"] - med["node_tick"], 4),
+                rounds={k_: [round(x, 4) for x in v] for k_, v in ms.items()},
+                invalid=int((buf["valid"] == 0).sum()), cycle_equals_tick=bool(same),
+                dropped=int((cyc["M"].cpu() != t(mode).cpu()).sum()),
+                failed=dict(cycle=int((cyc["st"] != 0).sum()), tick=int((tick["st"] != 0).sum())))), flush=True)
 
 
 def mission_sets(segs, nseg):
