@@ -597,6 +597,65 @@ int nmpc_batch_stage_bounds(nmpc_batch* b, void** table, size_t* bytes);
  * starts a fresh table. (Host-side switch: it applies to the launches enqueued after it.) */
 int nmpc_batch_clear_stage_bounds(nmpc_batch* b);
 
+/* Speed zones: the speed rows of the stage table from a speed map, on the device. A speed map is a grid mask in map
+ * coordinates, the shape fleet software uses for speed filters; the writer below looks up every stage of every
+ * processed robot's predicted horizon in it and writes a limit profile that the QP can follow, so a zoned fleet needs
+ * no host round trip per tick (csrc/speed_map.hip, DESIGN.md "Speed zones").
+ * The rule, for a processed robot i; the fp32 operations and their order are part of the contract (nothing is fused):
+ *   cap    the robot's own speed cap: ubx[0] of its column of the per-robot table while that table is on, else the
+ *          handle's ubx[0]; a = ubu[0] from the same source
+ *   g      = (slope * a) * (float)dt
+ *   c      the largest |carried[j][i]| over the speed reference states (diff, omni4: all NBX states; tric: the first)
+ *   stage k's position: rows k*NX and k*NX+1 of the resident iterate's xbar (RTI does not shift: this is the
+ *          linearisation point the stage-k box applies to); for a robot with reset[i] != 0, whose iterate is about to
+ *          be zeroed, pose[0..1][i] at every stage. In map coordinates (double)position + origin_i while the frame
+ *          table is on, else (double)position
+ *   cell   cx = floor((X - x0) / res), cy = floor((Y - y0) / res) in fp64 (half a cell below x0 is outside, not cell
+ *          0); off the grid or not finite: m_k = outside, else m_k = vmax[cy * w + cx]
+ *   z_k    = fminf(cap, fmaxf(v_floor, m_k)); a NaN cell therefore acts as v_floor
+ *   r_k    = min over j = k..N of (z_j + (float)(j - k) * g): a limit comes down along the horizon before the robot
+ *          reaches the zone, at most g per stage
+ *   lim_k  = fmaxf(r_k, c - (float)k * g), k = 0..N: the robot's current reference speed stays reachable
+ * Written: for k = 0..N the rows nmpc_batch_set_stage_limits' v_max writes, lbx = -lim_k and ubx = lim_k, and
+ * vlim[k*B + i] = lim_k when vlim is given. Not written: the input rows, tric's steering rows, and every row of a
+ * robot that was not processed.
+ * The caller's duties:
+ *   - A robot whose iterate holds no solution yet must be flagged in reset (its xbar is no prediction). In the node's
+ *     flow that always holds: the goal and path callbacks set the flag together with the new target.
+ *   - The map is configuration, not state: checkpoints carry the stage table (nmpc_batch_stage_bounds), not the map;
+ *     attach it again after a restore. The grid stays the caller's device memory and must outlive its use.
+ *   - With per-robot frames on, the map is in map coordinates and the frame table bridges; nothing else is needed.
+ * Out of scope: rotated or per-robot maps, maps for anything but the speed rows, the capsule ABI,
+ * nmpc_batch_solve_iterate's caller-held iterate (the writer reads the resident one), and any change to the solve
+ * kernels or to what a launch computes while no map is attached.
+ * Argument errors (NMPC_ERR_ARG): B out of range, map NULL, res <= 0 or not finite, w < 1, h < 1, vmax NULL, slope
+ * outside (0, 1], v_floor <= 0, reset without pose, a NULL handle. */
+typedef struct nmpc_speed_map {
+    double x0, y0;     /* map coordinates of the low corner of cell (0, 0) */
+    double res;        /* cell edge, m, > 0 */
+    int w, h;          /* cells along x, along y, >= 1 */
+    const float* vmax; /* [h][w] device, row cy, column cx: speed limit of the cell, m/s; +inf: none */
+    float outside;     /* the limit off the grid (default +inf) */
+} nmpc_speed_map;
+typedef struct nmpc_speed_rule {
+    float slope;   /* fraction of a_max * dt a limit may come down per stage, default 0.8 (the ramps' value) */
+    float v_floor; /* smallest limit ever written, default 0.05 m/s: a box must keep an interior */
+} nmpc_speed_rule;
+int nmpc_speed_map_default(nmpc_speed_map* map); /* zeros, outside = +inf */
+int nmpc_speed_rule_default(nmpc_speed_rule* rule);
+/* One launch on `stream`, no host synchronisation, through the stage table's writer path: the first call allocates and
+ * fills the table as every stage writer does. pose [3][B] frame values (required when reset is given), reset [B] or
+ * NULL, mask [B] or NULL (all), vlim [N+1][B] out or NULL; all device. */
+int nmpc_batch_stage_limits_from_map(nmpc_batch* b, int B, const nmpc_speed_map* map,
+                                     const nmpc_speed_rule* rule /* NULL: defaults */, const float* pose,
+                                     const unsigned char* reset, const unsigned char* mask, float* vlim, void* stream);
+/* Attach (a copy of the structs; the grid stays the caller's device memory) or detach (map NULL) the handle's speed
+ * map. While a map is attached, nmpc_batch_node_cycle runs the writer between the input stage and the tick, on the
+ * stage's fp32 pose and the cycle's reset array, for exactly the robots whose mode at that point is GOTO_POSE or
+ * FOLLOW_PATH (under strict an invalid robot is ERROR by then, so its rows stay bit for bit). While none is attached
+ * the cycle enqueues the launches it enqueued without this interface and allocates no stage table. */
+int nmpc_batch_set_speed_map(nmpc_batch* b, const nmpc_speed_map* map, const nmpc_speed_rule* rule /* NULL: defaults */);
+
 /* Per-robot model parameters. A fleet of one model family mixes vehicles: two wheelbases of the same differential
  * base, loaded and empty trucks whose tau_v differ by a factor of two or three (the reference runs one node per robot,
  * each sending its own geometry and time constants through {name}_acados_update_params, NMPCNavControlDiff.cpp:44-46,

@@ -92,6 +92,17 @@ class StageBoundsStruct(ctypes.Structure):
     _fields_ = [("lbx", c_void_p), ("ubx", c_void_p), ("lbu", c_void_p), ("ubu", c_void_p)]
 
 
+class SpeedMapStruct(ctypes.Structure):
+    """Mirror of nmpc_speed_map (include/nmpc_amd/nmpc_batch.h): vmax a device pointer [h][w]."""
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("res", ctypes.c_double), ("w", ctypes.c_int),
+                ("h", ctypes.c_int), ("vmax", c_void_p), ("outside", ctypes.c_float)]
+
+
+class SpeedRuleStruct(ctypes.Structure):
+    """Mirror of nmpc_speed_rule (include/nmpc_amd/nmpc_batch.h)."""
+    _fields_ = [("slope", ctypes.c_float), ("v_floor", ctypes.c_float)]
+
+
 # NMPC_NODE_* (a robot's state in the node's state machine) and NMPC_NODE_EV_* (what the tick did for it)
 NODE_IDLE, NODE_GOTO_POSE, NODE_FOLLOW_PATH, NODE_BREAK, NODE_ERROR = 0, 1, 2, 3, 4
 (NODE_EV_NONE, NODE_EV_SOLVED, NODE_EV_ARRIVED, NODE_EV_GOAL_TOO_FAR, NODE_EV_OFF_PATH, NODE_EV_SOLVE_FAILED,
@@ -131,6 +142,8 @@ BATCH_SYMBOLS = [
     "nmpc_batch_clear_robot_params",
     "nmpc_batch_set_stage_bounds", "nmpc_batch_set_stage_limits", "nmpc_batch_shift_stage_bounds",
     "nmpc_batch_stage_bounds", "nmpc_batch_clear_stage_bounds",
+    "nmpc_speed_map_default", "nmpc_speed_rule_default", "nmpc_batch_stage_limits_from_map",
+    "nmpc_batch_set_speed_map",
     "nmpc_batch_set_robot_model", "nmpc_batch_robot_model", "nmpc_batch_clear_robot_model",
     "nmpc_batch_set_robot_frame", "nmpc_batch_recentre", "nmpc_batch_to_frame", "nmpc_batch_from_frame",
     "nmpc_batch_robot_frame", "nmpc_batch_clear_robot_frame",
@@ -221,6 +234,11 @@ def lib():
     L.nmpc_batch_shift_stage_bounds.argtypes = [vp, i, i, vp, vp]
     L.nmpc_batch_stage_bounds.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
     L.nmpc_batch_clear_stage_bounds.argtypes = [vp]
+    SM, SR = ctypes.POINTER(SpeedMapStruct), ctypes.POINTER(SpeedRuleStruct)
+    L.nmpc_speed_map_default.argtypes = [SM]
+    L.nmpc_speed_rule_default.argtypes = [SR]
+    L.nmpc_batch_stage_limits_from_map.argtypes = [vp, i, SM, SR, vp, vp, vp, vp, vp]
+    L.nmpc_batch_set_speed_map.argtypes = [vp, SM, SR]
     L.nmpc_batch_set_robot_model.argtypes = [vp, i, vp, vp, vp]
     L.nmpc_batch_robot_model.argtypes = [vp, ctypes.POINTER(vp), c_int_p, c_int_p]
     L.nmpc_batch_clear_robot_model.argtypes = [vp]

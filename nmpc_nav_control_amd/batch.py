@@ -9,8 +9,8 @@ import ctypes
 import torch
 
 from ._lib import (KERNELS, MODEL_IDS, PLAN_MODES, REC_LAYOUTS, SCHEDULES, FleetRenew, FleetStats, LaunchPlan,
-                   ModelParams, NodeInputStruct, NodeParamsStruct, RobotParamsStruct, StageBoundsStruct, check,
-                   default_params, lib, model_dims)
+                   ModelParams, NodeInputStruct, NodeParamsStruct, RobotParamsStruct, SpeedMapStruct, SpeedRuleStruct,
+                   StageBoundsStruct, check, default_params, lib, model_dims)
 
 
 def _ptr(t, dtype=None, shape=None, name="argument"):
@@ -111,6 +111,24 @@ class NodeInput:
         return self.c
 
 
+class SpeedMap:
+    """nmpc_speed_map (include/nmpc_amd/nmpc_batch.h): a grid of speed limits in map coordinates. (x0, y0) is the low
+    corner of cell (0, 0), res the cell edge in metres, vmax a float32 device tensor [h][w] (row cy, column cx; +inf: no
+    limit), which this object keeps alive; outside is the limit off the grid."""
+
+    def __init__(self, x0, y0, res, vmax, outside=float("inf")):
+        if vmax is None or vmax.dim() != 2:
+            raise ValueError("vmax: expected a device tensor [h][w]")
+        self.vmax = vmax
+        h, w = vmax.shape
+        self.c = SpeedMapStruct(x0=float(x0), y0=float(y0), res=float(res), w=int(w), h=int(h),
+                                vmax=_ptr(vmax, F32, (h, w), "vmax"), outside=float(outside))
+
+
+def _speed_rule(slope, v_floor):
+    return SpeedRuleStruct(slope=float(slope), v_floor=float(v_floor))
+
+
 class BatchSolver:
     """B independent OCP instances of one model, solved in lockstep on one GPU.
 
@@ -133,6 +151,7 @@ class BatchSolver:
         self.nx, self.nu, self.ny, self.nbx, self.nbu = d["nx"], d["nu"], d["ny"], d["nbx"], d["nbu"]
         self.np = d["np"]
         self._h = ctypes.c_void_p()
+        self._speed_map = None  # the attached SpeedMap (set_speed_map): its grid is the library's to read
         with torch.cuda.device(self.device):
             check(lib().nmpc_batch_create(ctypes.byref(self.params), self.capacity, ctypes.byref(self._h)),
                   "nmpc_batch_create")
@@ -288,6 +307,38 @@ class BatchSolver:
         B = self.capacity if B is None else int(B)
         check(lib().nmpc_batch_shift_stage_bounds(self._h, B, int(n), _ptr(mask, U8, (B,), "mask"), _stream(stream)),
               "nmpc_batch_shift_stage_bounds")
+
+    def stage_limits_from_map(self, map, pose=None, reset=None, mask=None, vlim=None, slope=0.8, v_floor=0.05, B=None,
+                              stream=None):
+        """The speed rows of the stage table from a SpeedMap (nmpc_batch_stage_limits_from_map): every stage of every
+        processed robot's resident horizon is looked up in the map and the limit comes down along the horizon by at
+        most slope * a_max * dt per stage, never below v_floor. pose float32 [3][B] and reset uint8 [B]: a robot with
+        reset != 0 is looked up at its pose (its iterate is about to be zeroed); mask uint8 [B] selects the robots
+        (None: all); vlim float32 [N+1][B] receives the limits. B: from pose, reset, mask or vlim, else the argument,
+        else the capacity. One launch on the stream."""
+        if reset is not None and pose is None:
+            raise ValueError("stage_limits_from_map: reset needs pose")
+        if B is None:
+            given = [(pose, 1), (reset, 0), (mask, 0), (vlim, 1)]
+            B = next((self._batch_of(t, ax) for t, ax in given if t is not None), self.capacity)
+        B = int(B)
+        rule = _speed_rule(slope, v_floor)
+        check(lib().nmpc_batch_stage_limits_from_map(
+            self._h, B, ctypes.byref(map.c), ctypes.byref(rule), _ptr(pose, F32, (3, B), "pose"),
+            _ptr(reset, U8, (B,), "reset"), _ptr(mask, U8, (B,), "mask"), _ptr(vlim, F32, (self.N + 1, B), "vlim"),
+            _stream(stream)), "nmpc_batch_stage_limits_from_map")
+
+    def set_speed_map(self, map, slope=0.8, v_floor=0.05):
+        """Attach a SpeedMap to the solver, or detach it (None) (nmpc_batch_set_speed_map): while one is attached,
+        node_cycle runs stage_limits_from_map between its input stage and its tick, for the robots in GOTO_POSE or
+        FOLLOW_PATH. The solver keeps the map object, and with it the grid, alive."""
+        if map is None:
+            check(lib().nmpc_batch_set_speed_map(self._h, None, None), "nmpc_batch_set_speed_map")
+        else:
+            rule = _speed_rule(slope, v_floor)
+            check(lib().nmpc_batch_set_speed_map(self._h, ctypes.byref(map.c), ctypes.byref(rule)),
+                  "nmpc_batch_set_speed_map")
+        self._speed_map = map
 
     def stage_bounds(self):
         """View of the stage table as opaque bytes [1][bytes] (uint8), or None while it is off
@@ -742,4 +793,4 @@ def _hip():
     return _hip_lib
 
 
-__all__ = ["BatchSolver", "ModelParams", "NodeInput", "NodeParams", "default_params"]
+__all__ = ["BatchSolver", "ModelParams", "NodeInput", "NodeParams", "SpeedMap", "default_params"]

@@ -86,6 +86,10 @@ struct nmpc_batch {
     NodeInputState in_st{};
     float *in_pose = nullptr, *in_vel = nullptr, *in_goal = nullptr, *in_steer = nullptr;
     unsigned char* in_valid = nullptr;
+    // the attached speed map and its rule (nmpc_batch_set_speed_map; smap_on false: none): the cycle's writer reads them
+    nmpc_speed_map smap{};
+    nmpc_speed_rule srule{};
+    bool smap_on = false;
 };
 
 namespace {
@@ -447,6 +451,58 @@ const char* no_limits(const float* v_max, const float* a_max, const float* alpha
                       const float* dalpha_max, const char* msg)
 {
     return (!v_max && !a_max && !alpha_min && !alpha_max && !dalpha_max) ? msg : nullptr;
+}
+
+nmpc_speed_rule speed_rule_default()
+{
+    nmpc_speed_rule r;
+    r.slope = 0.8f;     // the ramps' value (tests/stage_bound_cases.py SLOPE)
+    r.v_floor = 0.05f;
+    return r;
+}
+
+// the payload check of the speed map's two entry points: the failed check, or nullptr (rule may be NULL: defaults)
+const char* bad_speed_map(const nmpc_speed_map* m, const nmpc_speed_rule* r)
+{
+    if (!m) return "speed map is NULL";
+    if (!std::isfinite(m->res) || !(m->res > 0.0)) return "speed map: res must be finite and > 0";
+    if (m->w < 1 || m->h < 1) return "speed map: w and h must be >= 1";
+    if (!m->vmax) return "speed map: vmax is NULL";
+    if (r && !(r->slope > 0.0f && r->slope <= 1.0f)) return "speed rule: slope must be in (0, 1]";
+    if (r && !(r->v_floor > 0.0f)) return "speed rule: v_floor must be > 0";
+    return nullptr;
+}
+
+// the speed map's writer launch on the stage table (which is ready): its arguments from the handle's tables and state
+hipError_t speed_map_write(nmpc_batch* b, int B, const nmpc_speed_map& map, const nmpc_speed_rule& rule,
+                           const float* pose, const unsigned char* reset, const unsigned char* mask,
+                           const unsigned char* mode, float* vlim, hipStream_t s)
+{
+    SpeedMapArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.sb = b->sbounds.p;
+    a.d = sb_dims(b);
+    a.B = B;
+    a.nx = b->nx;
+    a.tric = b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0;
+    a.map = map;
+    a.slope = rule.slope;
+    a.v_floor = rule.v_floor;
+    a.dt = b->kp.dt;
+    a.cap = b->kp.ubx[0];
+    a.a = b->kp.ubu[0];
+    a.rp = b->rparams.view();
+    a.rp_ubx = b->rp.off[kRpUbx];
+    a.rp_ubu = b->rp.off[kRpUbu];
+    a.xbar = b->xbar;
+    a.carried = b->carried;
+    a.origin = b->rframe.view64();
+    a.pose = pose;
+    a.reset = reset;
+    a.mask = mask;
+    a.mode = mode;
+    a.vlim = vlim;
+    return launch_speed_map(a, s);
 }
 
 // nmpc_batch_robot_params / nmpc_batch_robot_model: the view of a row-major table, [rows][capacity]
@@ -1177,6 +1233,14 @@ int nmpc_batch_node_cycle(nmpc_batch* b, int B, const nmpc_node_params* np, cons
     float* const goal = goal_map ? b->in_goal : nullptr;
     int rc = node_input(b, B, in, mode, in->strict ? mode : nullptr, goal_map, goal, s, &r);
     if (rc) return rc;
+    if (b->smap_on) {
+        // speed zones: the stage limits of the robots that are about to solve, from the stage's pose (under strict an
+        // invalid robot's mode is ERROR by now: its rows stay)
+        if ((rc = sb_table(b, s))) return rc;
+        rc = hip_err(speed_map_write(b, B, b->smap, b->srule, r.pose, reset, nullptr, mode, nullptr, s),
+                     "speed_map launch");
+        if (rc) return rc;
+    }
     const float* const steer = b->prm.model == NMPC_MODEL_TRIC3AMR ? r.steer_out : nullptr;
     rc = node_tick(b, B, np, q, mode, r.pose, r.vel, steer, goal, segs, seg_stride, q ? nullptr : nseg, path_u, reset,
                    event, err, traj_out, n_solved, cmd, u0, status, qp_iter, qp_res, stream);
@@ -1285,6 +1349,46 @@ int nmpc_batch_stage_bounds(nmpc_batch* b, void** table, size_t* bytes)
 }
 
 int nmpc_batch_clear_stage_bounds(nmpc_batch* b) { return table_clear(b, &nmpc_batch::sbounds); }
+
+int nmpc_speed_map_default(nmpc_speed_map* map)
+{
+    if (!map) return set_err(NMPC_ERR_ARG, "speed map is NULL");
+    std::memset(map, 0, sizeof(*map));
+    map->outside = INFINITY;
+    return NMPC_OK;
+}
+
+int nmpc_speed_rule_default(nmpc_speed_rule* rule)
+{
+    if (!rule) return set_err(NMPC_ERR_ARG, "speed rule is NULL");
+    *rule = speed_rule_default();
+    return NMPC_OK;
+}
+
+int nmpc_batch_stage_limits_from_map(nmpc_batch* b, int B, const nmpc_speed_map* map, const nmpc_speed_rule* rule,
+                                     const float* pose, const unsigned char* reset, const unsigned char* mask,
+                                     float* vlim, void* stream)
+{
+    const TraceRange trace("nmpc_batch_stage_limits_from_map");
+    const char* bad = bad_speed_map(map, rule);
+    if (!bad && reset && !pose) bad = "speed map: reset needs pose";
+    return table_write(b, B, bad, sb_table, stream, "speed_map launch", [&](hipStream_t s) {
+        return speed_map_write(b, B, *map, rule ? *rule : speed_rule_default(), pose, reset, mask, nullptr, vlim, s);
+    });
+}
+
+int nmpc_batch_set_speed_map(nmpc_batch* b, const nmpc_speed_map* map, const nmpc_speed_rule* rule)
+{
+    if (map)
+        if (const char* bad = bad_speed_map(map, rule)) return set_err(NMPC_ERR_ARG, bad);
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    b->smap_on = map != nullptr;
+    if (map) {
+        b->smap = *map;
+        b->srule = rule ? *rule : speed_rule_default();
+    }
+    return NMPC_OK;
+}
 
 int nmpc_batch_set_robot_model(nmpc_batch* b, int B, const float* p, const unsigned char* mask, void* stream)
 {

@@ -147,6 +147,8 @@ __host__ __device__ inline size_t sb_at(int k, int row, int i, int cap, int rows
     return ((size_t)k * cap + i) * (size_t)rows + row;
 }
 __host__ __device__ inline size_t sb_stage_stride(int cap, int rows) { return (size_t)cap * rows; }
+// the slots of a box that a speed limit covers (nmpc_model_params_set_limits' v_max): tric's slot 1 is the steering's
+__host__ __device__ constexpr int sb_speed_rows(int tric, int nbx) { return tric ? 1 : nbx; }
 
 template <class M>
 size_t team_scratch_floats(int N, int stride);
@@ -202,6 +204,27 @@ hipError_t launch_sb_limits(float* sb, const SbDims& d, int B, int tric, const f
                             const float* alpha_min, const float* alpha_max, const float* dalpha_max,
                             const unsigned char* mask, hipStream_t stream);
 hipError_t launch_sb_shift(float* sb, const SbDims& d, int B, int n, const unsigned char* mask, hipStream_t stream);
+// The stage table's speed rows from a speed map (speed_map.hip, nmpc_batch_stage_limits_from_map: the rule is stated
+// there). Device pointers; the resident arrays have the stride d.cap, the caller's the stride B
+struct SpeedMapArgs {
+    float* sb;
+    SbDims d;
+    int B, nx, tric;
+    nmpc_speed_map map;
+    float slope, v_floor, dt;
+    float cap, a;            // the handle's ubx[0] and ubu[0] ...
+    const float* rp;         // ... or, while the per-robot table is on, the robot's column: rows rp_ubx and rp_ubu
+    int rp_ubx, rp_ubu;
+    const float* xbar;       // [(N+1)*nx][d.cap]
+    const float* carried;    // [nbx][d.cap]
+    const double* origin;    // the frame table [2][d.cap], or nullptr while it is off
+    const float* pose;       // [3][B], or nullptr (then reset is nullptr too)
+    const unsigned char* reset;  // [B] or nullptr
+    const unsigned char* mask;   // [B] or nullptr: all
+    const unsigned char* mode;   // [B] or nullptr; the cycle's: only GOTO_POSE and FOLLOW_PATH robots are processed
+    float* vlim;             // [N+1][B] or nullptr
+};
+hipError_t launch_speed_map(const SpeedMapArgs& a, hipStream_t stream);
 // The frame table fr [2][cap] (fp64: every robot's origin x, then y) and the resident iterate's position rows.
 // frame_set: the masked robots of the first B take a new origin and the x and y row of every stage of xbar
 // ([(N+1)*nx][cap]) becomes (float)((double)x + (o_old - o_new)). The new origin is origin[2][B]; or, with pose_map

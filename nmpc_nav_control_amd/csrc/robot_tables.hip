@@ -74,7 +74,7 @@ struct LimSrc {
 template <bool kPerStage, class At>
 __device__ inline void limits_body(At at, int i, int k, int N, int B, int nbx, int nbu, int tric, const LimSrc& s)
 {
-    const int nv = tric ? 1 : nbx, na = tric ? 1 : nbu;  // tric: slot 1 of each box is the steering's
+    const int nv = sb_speed_rows(tric, nbx), na = tric ? 1 : nbu;  // tric: slot 1 of each box is the steering's
     const size_t e = kPerStage ? (size_t)k * B + i : (size_t)i;
     const bool inp = !kPerStage || k < N;
     if (s.v_max) {

@@ -25,12 +25,17 @@ interleaved timed windows of each after a warm-up, median and spread; one JSON l
 With --cycle: nmpc_batch_node_cycle (the input stage, the node tick and the status rule in one call, from fp64 map
 samples) on --node's mixed fleet, against nmpc_batch_node_tick on a twin handle fed the inputs the stage emitted
 (prepared beforehand: what a caller with a host-side getInputData hands over), and the stage's and the listener's
-launches alone. Three interleaved rounds of each, the median; one JSON line per (B, fraction).
+launches alone. Three interleaved rounds of each, the median; one JSON line per (B, fraction). With --speed-map as
+well: two more handles of the same sizes run node_cycle in the same rounds, one with a seeded speed map attached
+(256 x 256 cells of 0.25 m about the fleet, limits in [0.15, 1), a fifth of the cells without one) and one with a map
+that holds no limit (the writer runs and the stage table is on, but the QPs are those without a map), and the map's
+writer (nmpc_batch_stage_limits_from_map) is timed alone: node_cycle_map_ms, node_cycle_open_map_ms and writer_ms next
+to the figures without a map.
 
 Poses of --nearest and --tick: the path points at the seeded nearest_u, displaced by a seeded offset of up to 0.1 m.
 
 usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick | --node | --mission |
-                                                                                     --cycle]
+                                                                                     --cycle [--speed-map]]
 """
 import argparse
 import json
@@ -132,6 +137,7 @@ def main(argv=None):
     ap.add_argument("--node", action="store_true")
     ap.add_argument("--mission", action="store_true")
     ap.add_argument("--cycle", action="store_true")
+    ap.add_argument("--speed-map", action="store_true", help="with --cycle: node_cycle with a speed map attached too")
     a = ap.parse_args(argv)
     if a.cycle:
         return cycle_bench(a)
@@ -309,6 +315,14 @@ def cycle_bench(a):
     stream = torch.cuda.current_stream()
     i32, f64, now, period = torch.int32, torch.float64, 1700000000000000000, 25000000
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    smap = None
+    if a.speed_map:
+        from nmpc_nav_control_amd.batch import SpeedMap
+        rng = np.random.default_rng(20250826)
+        grid = rng.uniform(0.15, 1.0, (256, 256)).astype(np.float32)
+        grid[rng.uniform(size=grid.shape) < 0.2] = np.inf
+        smap = SpeedMap(-32.0, -32.0, 0.25, t(grid))
+        smap_open = SpeedMap(-32.0, -32.0, 0.25, t(np.full((256, 256), np.inf, np.float32)))
     for B in (4096, 1024):
         segs, nseg, nu = seeded_paths(B)
         pose = seeded_poses(segs, nseg, nu).astype(np.float64)
@@ -361,17 +375,57 @@ def cycle_bench(a):
                                       u0=d["u0"], status=d["st"])
 
             steps = {"node_cycle": cycle_step, "node_tick": tick_step, "stage": stage_step, "push": push_step}
+            mapped = {}
+            if smap is not None:
+                # two more handles on the same fleet and samples: the seeded map attached, and a map without a limit
+                # (the table is on and the writer runs, but every box is the handle's: the same QPs as without a map)
+                vlim = torch.zeros(N + 1, B, device=dev)
+
+                def attach(m, fresh):
+                    d = handle()
+                    d["solver"].enable_input(4)
+                    d["solver"].push_samples(stamp - period, smp)
+                    d["solver"].push_samples(stamp, smp)
+                    d["solver"].set_speed_map(m)
+                    d["nin"] = NodeInput.default(now_ns=now, **{k_: torch.zeros_like(v) for k_, v in buf.items()})
+                    # the robots have no iterate yet, which the caller of a map flags: consumed by the first solve.
+                    # (Not on the handle whose map holds no limit: its ticks are to be those of the handle without one)
+                    d["fresh"] = torch.ones(B, dtype=torch.uint8, device=dev) if fresh else None
+                    return d
+
+                def map_cycle(d):
+                    d["solver"].node_cycle(npar, d["nin"], d["M"], goal_map=G, segs=d["S"], nseg=d["NS"],
+                                           path_u=d["U"], reset=d["fresh"], u0=d["u0"], status=d["st"])
+
+                mapped = dict(node_cycle_map=attach(smap, True), node_cycle_open_map=attach(smap_open, False))
+                for k_, d in mapped.items():
+                    steps[k_] = lambda d=d: map_cycle(d)
+                steps["writer"] = lambda: mapped["node_cycle_map"]["solver"].stage_limits_from_map(smap, pose=P,
+                                                                                                    vlim=vlim)
             ms = {k_: [] for k_ in steps}
             for _ in range(3):
                 for k_, fn in steps.items():
                     ms[k_].append(timed(fn, a.iters, stream))
             med = {k_: sorted(v)[1] for k_, v in ms.items()}
             same = all(torch.equal(cyc[k_], tick[k_]) for k_ in ("u0", "st", "M", "U"))
+            extra = {}
+            if smap is not None:
+                mp, op = mapped["node_cycle_map"], mapped["node_cycle_open_map"]
+                extra = dict(node_cycle_map_ms=round(med["node_cycle_map"], 4),
+                             node_cycle_open_map_ms=round(med["node_cycle_open_map"], 4),
+                             writer_ms=round(med["writer"], 4),
+                             open_map_minus_cycle_ms=round(med["node_cycle_open_map"] - med["node_cycle"], 4),
+                             map_minus_open_map_ms=round(med["node_cycle_map"] - med["node_cycle_open_map"], 4),
+                             limited_stages=round(float((vlim[:, t(act)] < 1.0).float().mean()), 3),
+                             open_map_equals_cycle=all(torch.equal(cyc[k_], op[k_]) for k_ in ("u0", "st", "M", "U")),
+                             failed_map=int((mp["st"] != 0).sum()),
+                             dropped_map=int((mp["M"].cpu() != t(mode).cpu()).sum()),
+                             error_map=int((mp["M"] == 4).sum()))
             print(json.dumps(dict(
                 metric="node cycle ms (diff N=%d)" % N, B=B, active=k, n_solved=int(nsolved.cpu()),
                 node_cycle_ms=round(med["node_cycle"], 4), node_tick_ms=round(med["node_tick"], 4),
                 stage_ms=round(med["stage"], 4), push_ms=round(med["push"], 4),
-                cycle_minus_tick_ms=round(med["node_cycle"] - med["node_tick"], 4),
+                cycle_minus_tick_ms=round(med["node_cycle"] - med["node_tick"], 4), **extra,
                 rounds={k_: [round(x, 4) for x in v] for k_, v in ms.items()},
                 invalid=int((buf["valid"] == 0).sum()), cycle_equals_tick=bool(same),
                 dropped=int((cyc["M"].cpu() != t(mode).cpu()).sum()),
