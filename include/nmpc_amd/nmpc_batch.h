@@ -656,6 +656,85 @@ int nmpc_batch_stage_limits_from_map(nmpc_batch* b, int B, const nmpc_speed_map*
  * the cycle enqueues the launches it enqueued without this interface and allocates no stage table. */
 int nmpc_batch_set_speed_map(nmpc_batch* b, const nmpc_speed_map* map, const nmpc_speed_rule* rule /* NULL: defaults */);
 
+/* Fleet separation: the speed rows of the stage table from the other robots' predictions. A robot that closes on
+ * another one slows down, as it does under a safety scanner's warning field: every stage of a processed robot's
+ * horizon gets a speed cap from the distance to the nearest "track" at the same time, and the speed map's rule turns
+ * the caps into a limit profile the QP can follow (csrc/separation.hip, DESIGN.md "Fleet separation"). A track is a
+ * predicted path in map coordinates: another robot's horizon (nmpc_batch_export_tracks; several handles write into one
+ * buffer at different columns), a person from a tracker, a standing obstacle (K = 0).
+ * The rule, for a processed robot i; the fp32 operations and their order are part of the contract (nothing is fused):
+ *   p_k, cap, g, c   exactly the speed map's: the position of stage k in fp32 frame values (pose[0..1][i] at every
+ *          stage for a robot with reset[i] != 0), the robot's speed cap, its ramp step and its carried speed; X_k, Y_k
+ *          the fp64 map coordinates of p_k ((double)p_k + origin_i while the frame table is on)
+ *   h_k    = p_{min(k+1, N)} - p_{min(k, N-1)}, the direction of travel, one fp32 subtraction per component; a reset
+ *          robot has h_k = 0. Driving backwards needs no special case
+ *   pair   every track j other than own_first + i, at track stage kk = min(k, K): dx = (float)(Tx - X_k),
+ *          dy = (float)(Ty - Y_k), q = dx*dx + dy*dy (mul, mul, add)
+ *   counts when q <= range*range (an fp32 product; a NaN fails, so a NaN or infinite track never counts) and, with
+ *          ahead_only, when hx == 0 && hy == 0 or dx*hx + dy*hy > 0 (a track exactly abeam does not count)
+ *   q_k    the minimum q over the counting pairs, +inf when there is none (min is exact: the kernel's tiles and culls
+ *          do not show in the bits)
+ *   gap_k  = sqrtf(q_k), correctly rounded
+ *   s_k    = gain * (gap_k - clearance)
+ *   zmap_k = fminf(cap, fmaxf(v_floor, m_k)), m_k the map's cell as in "Speed zones", +inf without a map
+ *   z_k    = fminf(zmap_k, fmaxf(v_floor, s_k))
+ *   r_k, lim_k from z_k as in the speed map's rule, and the same rows are written; vlim[k*B + i] = lim_k and
+ *          gap[k*B + i] = gap_k when given
+ * With M == 0, or when no pair counts, the writer writes exactly what nmpc_batch_stage_limits_from_map writes (without
+ * a map: cap, corrected by c). The steady gap behind a leader at speed v is clearance + v / gain.
+ * ahead_only: two robots side by side in adjacent aisles, or one that has just been passed, do not brake each other;
+ * a standing robot (h = 0) has no direction and counts every track in range.
+ * The caller's duties are the speed map's, and: the tracks are configuration, not state: checkpoints carry the stage
+ * table, not the tracks; the buffer stays the caller's device memory and must outlive its use.
+ * Out of scope: this is speed limiting, not collision avoidance: two robots head-on both come down to v_floor and
+ * keep creeping. No general constraints in the QP, no change to the solve kernels, no per-track radii (a caller with
+ * mixed vehicle sizes takes the largest clearance), no rotated footprints, not the capsule ABI, not
+ * nmpc_batch_solve_iterate's caller-held iterate, no spatial index over the map.
+ * Argument errors (NMPC_ERR_ARG): B out of range, tracks NULL, M < 0, K < 0, xy NULL with M > 0, own_first < -1,
+ * own_first >= 0 && own_first + B > M, gain not finite or <= 0, clearance not finite or < 0, range not finite or
+ * <= clearance, the speed map's payload checks when map is given and the speed rule's when rule is given, reset
+ * without pose, a NULL handle. */
+typedef struct nmpc_tracks {
+    const double* xy; /* [K+1][2][M] device, fp64 MAP coordinates: track j at stage k (k * dt from now) */
+    int M, K;         /* M >= 0 tracks (xy may be NULL when M == 0), K >= 0: robot stage k reads track stage min(k, K) */
+    int own_first;    /* robot i of the call is track own_first + i and skips it; -1: no track is the handle's */
+} nmpc_tracks;
+typedef struct nmpc_sep_rule {
+    float clearance;  /* m, >= 0: the centre distance at which the cap reaches 0 (default 0.6) */
+    float gain;       /* 1/s, > 0: cap = gain * (gap - clearance) (default 1.0, a one-second headway) */
+    float range;      /* m, finite, > clearance: a track farther away does not count (default 3.0) */
+    int ahead_only;   /* default 1: only tracks in the half plane of the robot's direction of travel count */
+} nmpc_sep_rule;
+int nmpc_tracks_default(nmpc_tracks* tracks); /* zeros, own_first -1 */
+int nmpc_sep_rule_default(nmpc_sep_rule* sep);
+/* The handle's resident horizons as tracks: one small launch that writes, for the robots i in [0, B) and the stages
+ * k = 0..K, xy[(k*2 + c)*M + first + i] = the position of stage min(k, N) as the speed map reads it (rows k*NX and
+ * k*NX+1 of the resident xbar, widened to fp64, plus the robot's origin while the frame table is on). A robot with
+ * reset[i] != 0, and, when mode is given, a robot whose mode[i] is neither GOTO_POSE nor FOLLOW_PATH, is a standing
+ * obstacle: pose[0..1][i] plus the origin at every stage. The export reads the resident state and changes nothing of
+ * it. pose [3][B] frame values, reset [B] or NULL, mode [B] or NULL; all device. Argument errors: first < 0 or
+ * first + B > M, K < 0, xy NULL, pose NULL while reset or mode is given, B out of range, a NULL handle. */
+int nmpc_batch_export_tracks(nmpc_batch* b, int B, const float* pose, const unsigned char* reset,
+                             const unsigned char* mode, double* xy, int M, int K, int first, void* stream);
+/* The writer: on `stream`, no host synchronisation, through the stage table's writer path (the first call allocates and
+ * fills the table, as nmpc_batch_stage_limits_from_map does). pose, reset, mask, vlim as there; gap [N+1][B] out or NULL. */
+int nmpc_batch_stage_limits_from_tracks(nmpc_batch* b, int B, const nmpc_tracks* tracks,
+                                        const nmpc_sep_rule* sep /* NULL: defaults */,
+                                        const nmpc_speed_map* map /* or NULL */,
+                                        const nmpc_speed_rule* rule /* NULL: defaults */, const float* pose,
+                                        const unsigned char* reset, const unsigned char* mask,
+                                        float* vlim /* [N+1][B] or NULL */, float* gap /* [N+1][B] or NULL */,
+                                        void* stream);
+/* Attach (a copy of the two structs; the buffer stays the caller's device memory) or detach (tracks NULL) the handle's
+ * tracks. While tracks are attached, nmpc_batch_node_cycle runs between the input stage and the tick: (1) with
+ * export_own, the export of the handle's robots [0, B) at own_first, on the stage's fp32 pose, the cycle's reset and
+ * mode and K = tracks.K (export_own requires own_first >= 0; the library treats the buffer as writable then); (2) the
+ * writer, with the attached speed map and its rule if there is one, for the robots whose mode at that point is
+ * GOTO_POSE or FOLLOW_PATH (the speed map's remark on strict applies unchanged). With only a map attached, or with
+ * nothing attached, the cycle enqueues exactly the launches it enqueued without this interface. */
+int nmpc_batch_set_tracks(nmpc_batch* b, const nmpc_tracks* tracks, const nmpc_sep_rule* sep /* NULL: defaults */,
+                          int export_own);
+
 /* Per-robot model parameters. A fleet of one model family mixes vehicles: two wheelbases of the same differential
  * base, loaded and empty trucks whose tau_v differ by a factor of two or three (the reference runs one node per robot,
  * each sending its own geometry and time constants through {name}_acados_update_params, NMPCNavControlDiff.cpp:44-46,

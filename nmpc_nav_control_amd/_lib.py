@@ -103,6 +103,17 @@ class SpeedRuleStruct(ctypes.Structure):
     _fields_ = [("slope", ctypes.c_float), ("v_floor", ctypes.c_float)]
 
 
+class TracksStruct(ctypes.Structure):
+    """Mirror of nmpc_tracks (include/nmpc_amd/nmpc_batch.h): xy a device pointer [K+1][2][M], fp64."""
+    _fields_ = [("xy", c_void_p), ("M", ctypes.c_int), ("K", ctypes.c_int), ("own_first", ctypes.c_int)]
+
+
+class SepRuleStruct(ctypes.Structure):
+    """Mirror of nmpc_sep_rule (include/nmpc_amd/nmpc_batch.h)."""
+    _fields_ = [("clearance", ctypes.c_float), ("gain", ctypes.c_float), ("range", ctypes.c_float),
+                ("ahead_only", ctypes.c_int)]
+
+
 # NMPC_NODE_* (a robot's state in the node's state machine) and NMPC_NODE_EV_* (what the tick did for it)
 NODE_IDLE, NODE_GOTO_POSE, NODE_FOLLOW_PATH, NODE_BREAK, NODE_ERROR = 0, 1, 2, 3, 4
 (NODE_EV_NONE, NODE_EV_SOLVED, NODE_EV_ARRIVED, NODE_EV_GOAL_TOO_FAR, NODE_EV_OFF_PATH, NODE_EV_SOLVE_FAILED,
@@ -144,6 +155,8 @@ BATCH_SYMBOLS = [
     "nmpc_batch_stage_bounds", "nmpc_batch_clear_stage_bounds",
     "nmpc_speed_map_default", "nmpc_speed_rule_default", "nmpc_batch_stage_limits_from_map",
     "nmpc_batch_set_speed_map",
+    "nmpc_tracks_default", "nmpc_sep_rule_default", "nmpc_batch_export_tracks",
+    "nmpc_batch_stage_limits_from_tracks", "nmpc_batch_set_tracks",
     "nmpc_batch_set_robot_model", "nmpc_batch_robot_model", "nmpc_batch_clear_robot_model",
     "nmpc_batch_set_robot_frame", "nmpc_batch_recentre", "nmpc_batch_to_frame", "nmpc_batch_from_frame",
     "nmpc_batch_robot_frame", "nmpc_batch_clear_robot_frame",
@@ -239,6 +252,12 @@ def lib():
     L.nmpc_speed_rule_default.argtypes = [SR]
     L.nmpc_batch_stage_limits_from_map.argtypes = [vp, i, SM, SR, vp, vp, vp, vp, vp]
     L.nmpc_batch_set_speed_map.argtypes = [vp, SM, SR]
+    TR, SP = ctypes.POINTER(TracksStruct), ctypes.POINTER(SepRuleStruct)
+    L.nmpc_tracks_default.argtypes = [TR]
+    L.nmpc_sep_rule_default.argtypes = [SP]
+    L.nmpc_batch_export_tracks.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, vp]
+    L.nmpc_batch_stage_limits_from_tracks.argtypes = [vp, i, TR, SP, SM, SR, vp, vp, vp, vp, vp, vp]
+    L.nmpc_batch_set_tracks.argtypes = [vp, TR, SP, i]
     L.nmpc_batch_set_robot_model.argtypes = [vp, i, vp, vp, vp]
     L.nmpc_batch_robot_model.argtypes = [vp, ctypes.POINTER(vp), c_int_p, c_int_p]
     L.nmpc_batch_clear_robot_model.argtypes = [vp]

@@ -9,8 +9,8 @@ import ctypes
 import torch
 
 from ._lib import (KERNELS, MODEL_IDS, PLAN_MODES, REC_LAYOUTS, SCHEDULES, FleetRenew, FleetStats, LaunchPlan,
-                   ModelParams, NodeInputStruct, NodeParamsStruct, RobotParamsStruct, SpeedMapStruct, SpeedRuleStruct,
-                   StageBoundsStruct, check, default_params, lib, model_dims)
+                   ModelParams, NodeInputStruct, NodeParamsStruct, RobotParamsStruct, SepRuleStruct, SpeedMapStruct,
+                   SpeedRuleStruct, StageBoundsStruct, TracksStruct, check, default_params, lib, model_dims)
 
 
 def _ptr(t, dtype=None, shape=None, name="argument"):
@@ -125,6 +125,25 @@ class SpeedMap:
                                 vmax=_ptr(vmax, F32, (h, w), "vmax"), outside=float(outside))
 
 
+class Tracks:
+    """nmpc_tracks (include/nmpc_amd/nmpc_batch.h): predicted paths in map coordinates, a float64 device tensor
+    xy [K+1][2][M] (track j at stage k, k * dt from now), which this object keeps alive; None: no tracks (M = 0).
+    own_first: robot i of a call is track own_first + i and skips it (-1: no track is the handle's)."""
+
+    def __init__(self, xy=None, own_first=-1):
+        if xy is not None and (xy.dim() != 3 or xy.shape[1] != 2):
+            raise ValueError("xy: expected a device tensor [K+1][2][M]")
+        self.xy = xy
+        K1, M = (1, 0) if xy is None else (xy.shape[0], xy.shape[2])
+        self.M, self.K = int(M), int(K1) - 1
+        self.c = TracksStruct(xy=_ptr(xy, F64, (K1, 2, M), "xy") if xy is not None else None, M=self.M, K=self.K,
+                              own_first=int(own_first))
+
+
+def _sep_rule(clearance, gain, range, ahead_only):
+    return SepRuleStruct(clearance=float(clearance), gain=float(gain), range=float(range), ahead_only=int(ahead_only))
+
+
 def _speed_rule(slope, v_floor):
     return SpeedRuleStruct(slope=float(slope), v_floor=float(v_floor))
 
@@ -152,6 +171,7 @@ class BatchSolver:
         self.np = d["np"]
         self._h = ctypes.c_void_p()
         self._speed_map = None  # the attached SpeedMap (set_speed_map): its grid is the library's to read
+        self._tracks = None     # the attached Tracks (set_tracks): likewise its buffer
         with torch.cuda.device(self.device):
             check(lib().nmpc_batch_create(ctypes.byref(self.params), self.capacity, ctypes.byref(self._h)),
                   "nmpc_batch_create")
@@ -339,6 +359,61 @@ class BatchSolver:
             check(lib().nmpc_batch_set_speed_map(self._h, ctypes.byref(map.c), ctypes.byref(rule)),
                   "nmpc_batch_set_speed_map")
         self._speed_map = map
+
+    def export_tracks(self, xy, first=0, pose=None, reset=None, mode=None, B=None, stream=None):
+        """The resident horizons of the robots [0, B) as tracks (nmpc_batch_export_tracks): the columns first ..
+        first + B - 1 of xy, float64 [K+1][2][M] in map coordinates, stage min(k, N) at k. pose float32 [3][B]; a robot
+        with reset != 0 (uint8 [B]) or, when mode (uint8 [B]) is given, one that is neither in GOTO_POSE nor in
+        FOLLOW_PATH is written at its pose at every stage. B: from pose, reset or mode, else the argument, else the
+        capacity. One launch on the stream."""
+        if (reset is not None or mode is not None) and pose is None:
+            raise ValueError("export_tracks: reset and mode need pose")
+        if xy is None or xy.dim() != 3 or xy.shape[1] != 2:
+            raise ValueError("xy: expected a device tensor [K+1][2][M]")
+        if B is None:
+            given = [(pose, 1), (reset, 0), (mode, 0)]
+            B = next((self._batch_of(t, ax) for t, ax in given if t is not None), self.capacity)
+        B = int(B)
+        K1, M = xy.shape[0], xy.shape[2]
+        check(lib().nmpc_batch_export_tracks(
+            self._h, B, _ptr(pose, F32, (3, B), "pose"), _ptr(reset, U8, (B,), "reset"), _ptr(mode, U8, (B,), "mode"),
+            _ptr(xy, F64, (K1, 2, M), "xy"), int(M), int(K1) - 1, int(first), _stream(stream)),
+            "nmpc_batch_export_tracks")
+
+    def stage_limits_from_tracks(self, tracks, map=None, pose=None, reset=None, mask=None, vlim=None, gap=None,
+                                 clearance=0.6, gain=1.0, range=3.0, ahead_only=1, slope=0.8, v_floor=0.05, B=None,
+                                 stream=None):
+        """The speed rows of the stage table from Tracks and, optionally, a SpeedMap
+        (nmpc_batch_stage_limits_from_tracks): every stage of every processed robot's horizon gets the cap
+        gain * (gap - clearance) from the gap to the nearest track within range at the same time (ahead_only: in the
+        half plane of its direction of travel), and the speed map's rule makes a limit profile of the caps. pose, reset,
+        mask, vlim, slope, v_floor as stage_limits_from_map; gap float32 [N+1][B] receives the gaps (+inf: no track
+        counts)."""
+        if reset is not None and pose is None:
+            raise ValueError("stage_limits_from_tracks: reset needs pose")
+        if B is None:
+            given = [(pose, 1), (reset, 0), (mask, 0), (vlim, 1), (gap, 1)]
+            B = next((self._batch_of(t, ax) for t, ax in given if t is not None), self.capacity)
+        B = int(B)
+        sep, rule = _sep_rule(clearance, gain, range, ahead_only), _speed_rule(slope, v_floor)
+        check(lib().nmpc_batch_stage_limits_from_tracks(
+            self._h, B, ctypes.byref(tracks.c), ctypes.byref(sep), ctypes.byref(map.c) if map is not None else None,
+            ctypes.byref(rule), _ptr(pose, F32, (3, B), "pose"), _ptr(reset, U8, (B,), "reset"),
+            _ptr(mask, U8, (B,), "mask"), _ptr(vlim, F32, (self.N + 1, B), "vlim"),
+            _ptr(gap, F32, (self.N + 1, B), "gap"), _stream(stream)), "nmpc_batch_stage_limits_from_tracks")
+
+    def set_tracks(self, tracks, export_own=False, clearance=0.6, gain=1.0, range=3.0, ahead_only=1):
+        """Attach Tracks to the solver, or detach them (None) (nmpc_batch_set_tracks): while they are attached,
+        node_cycle runs, between its input stage and its tick, export_tracks of its own robots at tracks.own_first (with
+        export_own) and stage_limits_from_tracks, with the attached speed map if there is one, for the robots in
+        GOTO_POSE or FOLLOW_PATH. The solver keeps the object, and with it the buffer, alive."""
+        if tracks is None:
+            check(lib().nmpc_batch_set_tracks(self._h, None, None, 0), "nmpc_batch_set_tracks")
+        else:
+            sep = _sep_rule(clearance, gain, range, ahead_only)
+            check(lib().nmpc_batch_set_tracks(self._h, ctypes.byref(tracks.c), ctypes.byref(sep), int(bool(export_own))),
+                  "nmpc_batch_set_tracks")
+        self._tracks = tracks
 
     def stage_bounds(self):
         """View of the stage table as opaque bytes [1][bytes] (uint8), or None while it is off
@@ -793,4 +868,4 @@ def _hip():
     return _hip_lib
 
 
-__all__ = ["BatchSolver", "ModelParams", "NodeInput", "NodeParams", "SpeedMap", "default_params"]
+__all__ = ["BatchSolver", "ModelParams", "NodeInput", "NodeParams", "SpeedMap", "Tracks", "default_params"]

@@ -90,6 +90,15 @@ struct nmpc_batch {
     nmpc_speed_map smap{};
     nmpc_speed_rule srule{};
     bool smap_on = false;
+    // fleet separation (nmpc_batch_set_tracks; trk_on false: none attached): the attached tracks and rule, whether the
+    // cycle exports the handle's own robots, and the writer's scratch, allocated at its first call: the q plane
+    // [N+1][capacity] and the track boxes [4][sep_boxes_m]
+    nmpc_tracks trk{};
+    nmpc_sep_rule seprule{};
+    bool trk_on = false, trk_export = false;
+    float* sep_q = nullptr;
+    double* sep_boxes = nullptr;
+    int sep_boxes_m = 0;
 };
 
 namespace {
@@ -461,6 +470,14 @@ nmpc_speed_rule speed_rule_default()
     return r;
 }
 
+// the speed rule's payload check (rule may be NULL: defaults)
+const char* bad_speed_rule(const nmpc_speed_rule* r)
+{
+    if (r && !(r->slope > 0.0f && r->slope <= 1.0f)) return "speed rule: slope must be in (0, 1]";
+    if (r && !(r->v_floor > 0.0f)) return "speed rule: v_floor must be > 0";
+    return nullptr;
+}
+
 // the payload check of the speed map's two entry points: the failed check, or nullptr (rule may be NULL: defaults)
 const char* bad_speed_map(const nmpc_speed_map* m, const nmpc_speed_rule* r)
 {
@@ -468,15 +485,43 @@ const char* bad_speed_map(const nmpc_speed_map* m, const nmpc_speed_rule* r)
     if (!std::isfinite(m->res) || !(m->res > 0.0)) return "speed map: res must be finite and > 0";
     if (m->w < 1 || m->h < 1) return "speed map: w and h must be >= 1";
     if (!m->vmax) return "speed map: vmax is NULL";
-    if (r && !(r->slope > 0.0f && r->slope <= 1.0f)) return "speed rule: slope must be in (0, 1]";
-    if (r && !(r->v_floor > 0.0f)) return "speed rule: v_floor must be > 0";
+    return bad_speed_rule(r);
+}
+
+nmpc_sep_rule sep_rule_default()
+{
+    nmpc_sep_rule r;
+    r.clearance = 0.6f;
+    r.gain = 1.0f;  // a one-second headway
+    r.range = 3.0f;
+    r.ahead_only = 1;
+    return r;
+}
+
+// the payload check of fleet separation's writer and attach: the failed check, or nullptr (sep may be NULL: defaults;
+// B < 0: the batch size is not known yet, own_first + B is checked by the call that knows it)
+const char* bad_tracks(const nmpc_tracks* t, const nmpc_sep_rule* r, int B)
+{
+    if (!t) return "tracks is NULL";
+    if (t->M < 0) return "tracks: M must be >= 0";
+    if (t->K < 0) return "tracks: K must be >= 0";
+    if (t->M > 0 && !t->xy) return "tracks: xy is NULL";
+    if (t->own_first < -1) return "tracks: own_first must be >= -1";
+    if (t->own_first >= 0 && B >= 0 && (long long)t->own_first + B > t->M) return "tracks: own_first + B exceeds M";
+    if (r && (!std::isfinite(r->gain) || !(r->gain > 0.0f))) return "separation rule: gain must be finite and > 0";
+    if (r && (!std::isfinite(r->clearance) || !(r->clearance >= 0.0f)))
+        return "separation rule: clearance must be finite and >= 0";
+    if (r && (!std::isfinite(r->range) || !(r->range > r->clearance)))
+        return "separation rule: range must be finite and > clearance";
     return nullptr;
 }
 
 // the speed map's writer launch on the stage table (which is ready): its arguments from the handle's tables and state
-hipError_t speed_map_write(nmpc_batch* b, int B, const nmpc_speed_map& map, const nmpc_speed_rule& rule,
+// (map nullptr and sep given: fleet separation without a map; sep: the q plane is ready on the stream)
+hipError_t speed_map_write(nmpc_batch* b, int B, const nmpc_speed_map* map, const nmpc_speed_rule& rule,
                            const float* pose, const unsigned char* reset, const unsigned char* mask,
-                           const unsigned char* mode, float* vlim, hipStream_t s)
+                           const unsigned char* mode, float* vlim, hipStream_t s, const nmpc_sep_rule* sep = nullptr,
+                           float* gap = nullptr)
 {
     SpeedMapArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -485,7 +530,7 @@ hipError_t speed_map_write(nmpc_batch* b, int B, const nmpc_speed_map& map, cons
     a.B = B;
     a.nx = b->nx;
     a.tric = b->prm.model == NMPC_MODEL_TRIC3AMR ? 1 : 0;
-    a.map = map;
+    if (map) a.map = *map;
     a.slope = rule.slope;
     a.v_floor = rule.v_floor;
     a.dt = b->kp.dt;
@@ -502,7 +547,83 @@ hipError_t speed_map_write(nmpc_batch* b, int B, const nmpc_speed_map& map, cons
     a.mask = mask;
     a.mode = mode;
     a.vlim = vlim;
+    if (sep) {
+        a.sep_q = b->sep_q;
+        a.sep_gain = sep->gain;
+        a.sep_clearance = sep->clearance;
+        a.gap = gap;
+    }
     return launch_speed_map(a, s);
+}
+
+// the scratch of fleet separation's writer: the q plane, and boxes for M tracks (a larger M takes a new allocation;
+// hipFree waits for the launches that read the old one)
+int sep_scratch(nmpc_batch* b, int M)
+{
+    if (!b->sep_q) {
+        const hipError_t e = hipMalloc(&b->sep_q, sizeof(float) * (size_t)(b->prm.N + 1) * (size_t)b->capacity);
+        if (e != hipSuccess) return hip_err(e, "hipMalloc");
+    }
+    if (M > b->sep_boxes_m) {
+        (void)hipFree(b->sep_boxes);
+        b->sep_boxes = nullptr;
+        b->sep_boxes_m = 0;
+        const hipError_t e = hipMalloc(&b->sep_boxes, sizeof(double) * 4 * (size_t)M);
+        if (e != hipSuccess) return hip_err(e, "hipMalloc");
+        b->sep_boxes_m = M;
+    }
+    return NMPC_OK;
+}
+
+hipError_t export_tracks(nmpc_batch* b, int B, const float* pose, const unsigned char* reset,
+                         const unsigned char* mode, double* xy, int M, int K, int first, hipStream_t s)
+{
+    ExportTracksArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.N = b->prm.N;
+    a.nx = b->nx;
+    a.cap = b->capacity;
+    a.xbar = b->xbar;
+    a.origin = b->rframe.view64();
+    a.pose = pose;
+    a.reset = reset;
+    a.mode = mode;
+    a.xy = xy;
+    a.M = M;
+    a.K = K;
+    a.first = first;
+    return launch_export_tracks(a, s);
+}
+
+// fleet separation's writer on the stage table and the scratch (both ready): the q plane, then the rule's launch
+hipError_t tracks_write(nmpc_batch* b, int B, const nmpc_tracks& t, const nmpc_sep_rule& sep, const nmpc_speed_map* map,
+                        const nmpc_speed_rule& rule, const float* pose, const unsigned char* reset,
+                        const unsigned char* mask, const unsigned char* mode, float* vlim, float* gap, hipStream_t s)
+{
+    SepArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.d = sb_dims(b);
+    a.B = B;
+    a.nx = b->nx;
+    a.xbar = b->xbar;
+    a.origin = b->rframe.view64();
+    a.pose = pose;
+    a.reset = reset;
+    a.mask = mask;
+    a.mode = mode;
+    a.xy = t.xy;
+    a.M = t.M;
+    a.K = t.K;
+    a.own_first = t.own_first;
+    a.ahead_only = sep.ahead_only ? 1 : 0;
+    a.range2 = sep.range * sep.range;
+    a.cull2 = (double)a.range2 * (1.0 + 1e-5);  // separation.hip: why this is conservative
+    a.boxes = b->sep_boxes;
+    a.q = b->sep_q;
+    const hipError_t e = launch_sep_min(a, s);
+    if (e != hipSuccess) return e;
+    return speed_map_write(b, B, map, rule, pose, reset, mask, mode, vlim, s, &sep, gap);
 }
 
 // nmpc_batch_robot_params / nmpc_batch_robot_model: the view of a row-major table, [rows][capacity]
@@ -755,7 +876,7 @@ int nmpc_batch_destroy(nmpc_batch* b)
     for (const DevTable* t : {&b->rparams, &b->sbounds, &b->rmodel, &b->rframe}) (void)hipFree(t->p);
     for (void* p : {(void*)b->in_st.stamp, (void*)b->in_st.sample, (void*)b->in_st.count, (void*)b->in_st.newest,
                     (void*)b->in_st.held, (void*)b->in_pose, (void*)b->in_vel, (void*)b->in_goal, (void*)b->in_steer,
-                    (void*)b->in_valid})
+                    (void*)b->in_valid, (void*)b->sep_q, (void*)b->sep_boxes})
         (void)hipFree(p);
     delete b;
     return NMPC_OK;
@@ -1227,17 +1348,32 @@ int nmpc_batch_node_cycle(nmpc_batch* b, int B, const nmpc_node_params* np, cons
     if (const int rc = node_tick_check(b, B, np, q, mode, &some, &some, segs, seg_stride, q ? nullptr : nseg, path_u, &go))
         return rc;
     if (!b->in_st.depth) return set_err(NMPC_ERR_ARG, "the input state is not enabled (nmpc_batch_enable_input)");
+    if (b->trk_on && b->trk.own_first >= 0 && (long long)b->trk.own_first + B > b->trk.M)
+        return set_err(NMPC_ERR_ARG, "tracks: own_first + B exceeds M");
     if (!go) return NMPC_OK;
     hipStream_t s = (hipStream_t)stream;
     nmpc_node_input r;
     float* const goal = goal_map ? b->in_goal : nullptr;
     int rc = node_input(b, B, in, mode, in->strict ? mode : nullptr, goal_map, goal, s, &r);
     if (rc) return rc;
-    if (b->smap_on) {
+    if (b->trk_on) {
+        // fleet separation: the handle's own horizons into the track buffer, then the stage limits of the robots that
+        // are about to solve from the tracks and, if one is attached, the speed map
+        if (b->trk_export) {
+            rc = hip_err(export_tracks(b, B, r.pose, reset, mode, const_cast<double*>(b->trk.xy), b->trk.M, b->trk.K,
+                                       b->trk.own_first, s), "export_tracks launch");
+            if (rc) return rc;
+        }
+        if ((rc = sb_table(b, s)) || (rc = sep_scratch(b, b->trk.M))) return rc;
+        rc = hip_err(tracks_write(b, B, b->trk, b->seprule, b->smap_on ? &b->smap : nullptr,
+                                  b->smap_on ? b->srule : speed_rule_default(), r.pose, reset, nullptr, mode, nullptr,
+                                  nullptr, s), "separation launch");
+        if (rc) return rc;
+    } else if (b->smap_on) {
         // speed zones: the stage limits of the robots that are about to solve, from the stage's pose (under strict an
         // invalid robot's mode is ERROR by now: its rows stay)
         if ((rc = sb_table(b, s))) return rc;
-        rc = hip_err(speed_map_write(b, B, b->smap, b->srule, r.pose, reset, nullptr, mode, nullptr, s),
+        rc = hip_err(speed_map_write(b, B, &b->smap, b->srule, r.pose, reset, nullptr, mode, nullptr, s),
                      "speed_map launch");
         if (rc) return rc;
     }
@@ -1373,7 +1509,7 @@ int nmpc_batch_stage_limits_from_map(nmpc_batch* b, int B, const nmpc_speed_map*
     const char* bad = bad_speed_map(map, rule);
     if (!bad && reset && !pose) bad = "speed map: reset needs pose";
     return table_write(b, B, bad, sb_table, stream, "speed_map launch", [&](hipStream_t s) {
-        return speed_map_write(b, B, *map, rule ? *rule : speed_rule_default(), pose, reset, mask, nullptr, vlim, s);
+        return speed_map_write(b, B, map, rule ? *rule : speed_rule_default(), pose, reset, mask, nullptr, vlim, s);
     });
 }
 
@@ -1386,6 +1522,67 @@ int nmpc_batch_set_speed_map(nmpc_batch* b, const nmpc_speed_map* map, const nmp
     if (map) {
         b->smap = *map;
         b->srule = rule ? *rule : speed_rule_default();
+    }
+    return NMPC_OK;
+}
+
+int nmpc_tracks_default(nmpc_tracks* tracks)
+{
+    if (!tracks) return set_err(NMPC_ERR_ARG, "tracks is NULL");
+    std::memset(tracks, 0, sizeof(*tracks));
+    tracks->own_first = -1;
+    return NMPC_OK;
+}
+
+int nmpc_sep_rule_default(nmpc_sep_rule* sep)
+{
+    if (!sep) return set_err(NMPC_ERR_ARG, "separation rule is NULL");
+    *sep = sep_rule_default();
+    return NMPC_OK;
+}
+
+int nmpc_batch_export_tracks(nmpc_batch* b, int B, const float* pose, const unsigned char* reset,
+                             const unsigned char* mode, double* xy, int M, int K, int first, void* stream)
+{
+    const TraceRange trace("nmpc_batch_export_tracks");
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (first < 0 || (long long)first + B > M) return set_err(NMPC_ERR_ARG, "export tracks: first out of range [0, M - B]");
+    if (K < 0) return set_err(NMPC_ERR_ARG, "export tracks: K must be >= 0");
+    if (!xy) return set_err(NMPC_ERR_ARG, "export tracks: xy is NULL");
+    if ((reset || mode) && !pose) return set_err(NMPC_ERR_ARG, "export tracks: reset and mode need pose");
+    if (const int rc = check_batch(b, B)) return rc;
+    if (B == 0) return NMPC_OK;
+    return hip_err(export_tracks(b, B, pose, reset, mode, xy, M, K, first, (hipStream_t)stream), "export_tracks launch");
+}
+
+int nmpc_batch_stage_limits_from_tracks(nmpc_batch* b, int B, const nmpc_tracks* tracks, const nmpc_sep_rule* sep,
+                                        const nmpc_speed_map* map, const nmpc_speed_rule* rule, const float* pose,
+                                        const unsigned char* reset, const unsigned char* mask, float* vlim, float* gap,
+                                        void* stream)
+{
+    const TraceRange trace("nmpc_batch_stage_limits_from_tracks");
+    const char* bad = bad_tracks(tracks, sep, B);
+    if (!bad) bad = map ? bad_speed_map(map, rule) : bad_speed_rule(rule);
+    if (!bad && reset && !pose) bad = "tracks: reset needs pose";
+    return table_write(b, B, bad, sb_table, stream, "separation launch", [&](hipStream_t s) {
+        if (sep_scratch(b, tracks->M)) return hipErrorOutOfMemory;
+        return tracks_write(b, B, *tracks, sep ? *sep : sep_rule_default(), map, rule ? *rule : speed_rule_default(),
+                            pose, reset, mask, nullptr, vlim, gap, s);
+    });
+}
+
+int nmpc_batch_set_tracks(nmpc_batch* b, const nmpc_tracks* tracks, const nmpc_sep_rule* sep, int export_own)
+{
+    if (tracks) {
+        if (const char* bad = bad_tracks(tracks, sep, -1)) return set_err(NMPC_ERR_ARG, bad);
+        if (export_own && tracks->own_first < 0) return set_err(NMPC_ERR_ARG, "tracks: export_own needs own_first >= 0");
+    }
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    b->trk_on = tracks != nullptr;
+    if (tracks) {
+        b->trk = *tracks;
+        b->seprule = sep ? *sep : sep_rule_default();
+        b->trk_export = export_own != 0;
     }
     return NMPC_OK;
 }

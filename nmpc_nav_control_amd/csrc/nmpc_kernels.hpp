@@ -223,8 +223,45 @@ struct SpeedMapArgs {
     const unsigned char* mask;   // [B] or nullptr: all
     const unsigned char* mode;   // [B] or nullptr; the cycle's: only GOTO_POSE and FOLLOW_PATH robots are processed
     float* vlim;             // [N+1][B] or nullptr
+    // fleet separation's operand (nmpc_batch_stage_limits_from_tracks), or nullptr: q_k [N+1][d.cap], written by
+    // launch_sep_min for the same robots; then map.vmax may be nullptr (no map), and gap [N+1][B] or nullptr is written
+    const float* sep_q;
+    float sep_gain, sep_clearance;
+    float* gap;
 };
 hipError_t launch_speed_map(const SpeedMapArgs& a, hipStream_t stream);
+// Fleet separation (separation.hip; the rule is stated at nmpc_batch_stage_limits_from_tracks). The export of the
+// resident horizons into a track buffer xy [K+1][2][M] at the columns first..first+B-1
+struct ExportTracksArgs {
+    int B, N, nx, cap;
+    const float* xbar;           // [(N+1)*nx][cap]
+    const double* origin;        // the frame table [2][cap], or nullptr while it is off
+    const float* pose;           // [3][B], or nullptr (then reset and mode are nullptr too)
+    const unsigned char* reset;  // [B] or nullptr
+    const unsigned char* mode;   // [B] or nullptr
+    double* xy;
+    int M, K, first;
+};
+hipError_t launch_export_tracks(const ExportTracksArgs& a, hipStream_t stream);
+// q_k, the squared distance from stage k of every processed robot to its nearest counting track (+inf: none), into
+// q [N+1][d.cap]: the box prepass over the tracks (boxes [4][M], handle-owned scratch) and the culled minimum
+struct SepArgs {
+    SbDims d;
+    int B, nx;
+    const float* xbar;
+    const double* origin;
+    const float* pose;
+    const unsigned char* reset;
+    const unsigned char* mask;
+    const unsigned char* mode;  // as SpeedMapArgs': the same robots are processed
+    const double* xy;           // [K+1][2][M]
+    int M, K, own_first, ahead_only;
+    float range2;               // range * range, one fp32 product
+    double cull2;               // a track whose box is farther than this (squared) from the robot's is skipped
+    double* boxes;
+    float* q;
+};
+hipError_t launch_sep_min(const SepArgs& a, hipStream_t stream);
 // The frame table fr [2][cap] (fp64: every robot's origin x, then y) and the resident iterate's position rows.
 // frame_set: the masked robots of the first B take a new origin and the x and y row of every stage of xbar
 // ([(N+1)*nx][cap]) becomes (float)((double)x + (o_old - o_new)). The new origin is origin[2][B]; or, with pose_map

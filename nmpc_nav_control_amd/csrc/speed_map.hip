@@ -10,6 +10,9 @@
 // Phase 2, behind a block barrier: a lane evaluates the closed form min_j (z_j + (j - k) g) for each of its stages,
 // one multiply and one add per candidate. min is exact, so the mapping does not show in the bits; the file is compiled
 // without contraction (Makefile), so neither does the compiler.
+// Fleet separation (separation.hip, nmpc_batch_stage_limits_from_tracks) reaches the rule through one optional
+// operand: sep_q, the squared distance to the nearest counting track per stage, caps z_k before phase 2. The map is
+// optional then (vmax nullptr: no cell limits). With sep_q nullptr the kernel computes what it computed without it.
 #include "nmpc_kernels.hpp"
 
 namespace nmpc {
@@ -64,8 +67,16 @@ __global__ void __launch_bounds__(kThreads) k_speed_map(SpeedMapArgs a, int R)
 #pragma unroll
             for (int u = 0; u < kChunk; u++) {
                 const int k = k0 + u * L;
-                const float m = cell_limit(a.map, (double)x[u] + ox, (double)y[u] + oy);
-                if (k <= N) zs[(size_t)k * R + row] = fminf(vcap, fmaxf(a.v_floor, m));
+                // (no map: m_k = +inf, the limit is the cap)
+                const float m = a.map.vmax ? cell_limit(a.map, (double)x[u] + ox, (double)y[u] + oy) : INFINITY;
+                float z = fminf(vcap, fmaxf(a.v_floor, m));
+                if (a.sep_q && k <= N) {  // fleet separation: the cap from the gap to the nearest counting track
+                    const float gap = sqrtf(a.sep_q[(size_t)k * cap + i]);
+                    const float sk = a.sep_gain * (gap - a.sep_clearance);
+                    z = fminf(z, fmaxf(a.v_floor, sk));
+                    if (a.gap) a.gap[(size_t)k * a.B + i] = gap;
+                }
+                if (k <= N) zs[(size_t)k * R + row] = z;
             }
         }
     }

@@ -3,7 +3,7 @@
 table off and with the table on holding the handle's own values, i.e. the same QPs, and the cost of one launch of each
 of the table's writers. One JSON line per measurement.
 
-usage: python tools/bench_tables.py --table robot_params|stage_bounds|robot_model|frame
+usage: python tools/bench_tables.py --table robot_params|stage_bounds|robot_model|frame|separation
                                     [--config metric|diff1024|omni4|tric] [--model diff] [--batch 4096] [--N 40]
                                     [--steps 100] [--warmup 240] [--repeats 3]
 --config names a (model, batch, N) of bench.py (default metric: diff, 4096, 40); --model, --batch and --N replace its
@@ -20,6 +20,12 @@ state; `rate` is robot ticks per second over the timed steps (solve + plant step
                 robot, the segments moved there in fp64, the same fp32 poses); `us_per_tick` is the mean over the
                 timed ticks, launched back to back;   writers: set_robot_frame, recentre (a radius that moves every
                 robot, then one that moves none), to_frame and from_frame of a pose and of a trajectory
+  separation    fleet separation (nmpc_batch_export_tracks + nmpc_batch_stage_limits_from_tracks before every tick,
+                the fleet's own export as the tracks, M = B): off, spread (every robot its own origin on a square grid
+                of 10 m pitch: nobody is in range of anybody), dense (a pitch of 1.33 m: about 16 tracks within the
+                3 m range of every robot). The three variants have the frame table on with the same origins as their
+                `off`, so the tick is the same; `sep_us` is export + writer alone, timed back to back on the final
+                state, and `cull` what the box test kept, counted by tests/separation_ref.py on 256 of the robots
 The writers are timed on 4096 robots with a mask on half of them: mean over 200 back-to-back launches."""
 import argparse
 import itertools
@@ -35,7 +41,9 @@ from nmpc_nav_control_amd.batch import BatchSolver, NodeParams  # noqa: E402
 from nmpc_nav_control_amd.fleet import Fleet  # noqa: E402
 from nmpc_nav_control_amd.scenario import DEFAULT_SEED, PARAMS  # noqa: E402
 from nmpc_nav_control_amd.path import PathQueue  # noqa: E402
+from nmpc_nav_control_amd.batch import Tracks  # noqa: E402
 from tests import frame_cases  # noqa: E402  (the origins, stated once)
+from tests import separation_ref  # noqa: E402
 from tests.path_cases import random_paths  # noqa: E402
 from tests.path_nearest_ref import near_err  # noqa: E402
 from tests.robot_model_cases import P0, P1, P2  # noqa: E402  (the rule's factors, stated once)
@@ -117,6 +125,7 @@ TABLES = {
     "robot_model": (dict(off=None, uniform=lambda s, B, dev: s.set_robot_model(model_table(s, B, False, dev)),
                          rule=lambda s, B, dev: s.set_robot_model(model_table(s, B, True, dev))), rm_writers),
     "frame": (dict(off=False, on=True), fr_writers),
+    "separation": (dict(off=None, spread=None, dense=None), None),
 }
 
 
@@ -137,6 +146,55 @@ def timed(model, B, N, steps, warmup, label, fill, dev):
     fails = int((f.status != 0).sum().item())
     return dict(model=model, B=B, N=N, table=label, steps=steps, ms_per_step=round(ms / steps, 4),
                 rate=round(B * steps / ms * 1e3, 1), failed_last_tick=fails, plan=f.solver.plan_ex(B, "run")["kernel"])
+
+
+SEP_PITCH = dict(off=10.0, spread=10.0, dense=1.33)
+
+
+def timed_separation(model, B, N, steps, warmup, label, dev):
+    """the closed loop with export + writer before every tick (label off: without them), every robot's origin on a grid"""
+    f = Fleet(model, B, N, DEFAULT_SEED, dev)
+    s = f.solver
+    side = int(np.ceil(np.sqrt(B)))
+    i = np.arange(B)
+    origin = SEP_PITCH[label] * np.stack([i % side, i // side]).astype(np.float64)
+    s.set_robot_frame(torch.from_numpy(origin).to(dev))
+    xy = torch.zeros(N + 1, 2, B, dtype=torch.float64, device=dev)
+    tr = Tracks(xy, own_first=0)
+
+    def sep():
+        s.export_tracks(xy, first=0, pose=f.pose, reset=f.reset)
+        s.stage_limits_from_tracks(tr, pose=f.pose, reset=f.reset)
+
+    def tick():
+        if label != "off":
+            sep()
+        f.tick()
+    for _ in range(warmup):
+        tick()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(steps):
+        tick()
+    b.record()
+    torch.cuda.synchronize()
+    ms = a.elapsed_time(b)
+    r = dict(model=model, B=B, N=N, table=label, steps=steps, ms_per_step=round(ms / steps, 4),
+             rate=round(B * steps / ms * 1e3, 1), failed_last_tick=int((f.status != 0).sum().item()))
+    if label != "off":
+        a.record()
+        for _ in range(20):
+            sep()
+        b.record()
+        torch.cuda.synchronize()
+        r["sep_us"] = round(a.elapsed_time(b) / 20 * 1e3, 1)
+        T = xy.cpu().numpy()
+        pick = np.arange(0, B, max(1, B // 256))[:256]
+        c = separation_ref.cull_counts_map(T[:, :, pick], T, own=pick)
+        r["cull"] = dict(box_tests=int(c["box_tests"]), kept_mean=round(float(c["kept"].mean()), 2),
+                         kept_max=int(c["kept"].max()), pair_evals_mean=round(float(c["pair_evals"].mean()), 1))
+    return r
 
 
 def path_fleet(B, S=4, seed=DEFAULT_SEED):
@@ -234,9 +292,13 @@ def main():
                 for r in timed_path_ticks(model, B, N, args.steps, args.warmup, label, fill, dev):
                     print(json.dumps(dict(r, repeat=rep)), flush=True)
                 continue
+            if args.table == "separation":
+                print(json.dumps(dict(timed_separation(model, B, N, args.steps, args.warmup, label, dev), repeat=rep)),
+                      flush=True)
+                continue
             r = timed(model, B, N, args.steps, args.warmup, label, fill, dev)
             print(json.dumps(dict(r, **tag, repeat=rep)), flush=True)
-    for r in writer_launches(writers, model, N, dev):
+    for r in writer_launches(writers, model, N, dev) if writers else ():
         print(json.dumps(r), flush=True)
 
 
