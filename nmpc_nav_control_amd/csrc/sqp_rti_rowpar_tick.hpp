@@ -1003,6 +1003,27 @@
             __syncthreads();  // the boundary states and costates
             RP_MSTAMP(7, 0);
             RP_STAMP(5 + 4 * it);
+            // The master's factorisations work in fp64 on the segments' value matrices, whose entries carry the barrier
+            // weights Sigma = lambda / t. A bound that lies exactly on the iterate (ub - zbar == 0: a robot held on its
+            // speed limit at a fixed point of its loop) has the solution z = 0, so nothing floors its slack: t follows
+            // mu / lambda down (5e-12 at mu = 4e-10) and Sigma passes 1e13 beside free slots at 1, K = I + L' C L
+            // loses a unit pivot to rounding, and rowchol poisons the factor (mst_qform). That is the breakdown phase
+            // B's pivot test reports, one phase later, and it gets phase B's rule: with the iterate converged (mu,
+            // res_ineq) the solve ends here, on the iterate before the broken step; otherwise status 1, as the NaN test
+            // of the next iteration gave it. (Without this the NaN direction was applied first, and a nearly converged
+            // solve failed: DESIGN.md "Speed zones", A robot on its limit.) The test reads the join's s_m and lam_m: a
+            // poisoned factor of either sweep reaches both through Phat_m / Shat_m, and the join's own factor makes
+            // every entry of lam_m NaN (Q = Y Y' has the poisoned rows of Y in every row's products); the master stays
+            // as it was.
+            const float jn = Sg > 1 ? sl[mj * 2 * NX] + sl[mj * 2 * NX + 2 * NX - 1] : 0.0f;
+            if (jn != jn) {
+                status = (mu <= kBreakdownMuT && res_ineq <= P.tol_ineq * 10.0f) ? 0 : 1;
+                float cm;
+                adjoint(res_stat, cm);
+                exit_res[0] = res_stat;
+                it_done = it;
+                break;
+            }
 
             // ---- phase C (segments in parallel, 0 -> N): row q starts at x_{qL} = s_q and takes the stored
             // factor with LR + Z lam_{q+1}; rows other than the last stop before the next segment's first stage

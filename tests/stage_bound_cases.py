@@ -68,9 +68,10 @@ def spliced_qp(o, xbar, ubar, x0, yref, We, box):
     return q
 
 
-def solve_spliced(o, xbar, ubar, x0, yref, We, box):
+def solve_spliced(o, xbar, ubar, x0, yref, We, box, return_sol=False):
     """One SQP-RTI iteration on the spliced QP: (status, qp_iter, xbar_new, ubar_new), the iterate unchanged unless
-    status == 0 (oc_sqp_rti_ex's rule)."""
+    status == 0 (oc_sqp_rti_ex's rule). return_sol: the QP's solution arrays (du, dx, pi, the bound multipliers and
+    slacks) as a fifth value."""
     N, nx, nu = o.N, o.nx, o.nu
     q = spliced_qp(o, xbar, ubar, x0, yref, We, box)
     qp = OcQp(N, *[_dp(q[k]) for k in _QP_KEYS])
@@ -85,6 +86,8 @@ def solve_spliced(o, xbar, ubar, x0, yref, We, box):
     if status == 0:
         xb += arrs["dx"]
         ub += arrs["du"]
+    if return_sol:
+        return status, st.qp_iter, xb, ub, arrs
     return status, st.qp_iter, xb, ub
 
 

@@ -30,12 +30,15 @@ well: two more handles of the same sizes run node_cycle in the same rounds, one 
 (256 x 256 cells of 0.25 m about the fleet, limits in [0.15, 1), a fifth of the cells without one) and one with a map
 that holds no limit (the writer runs and the stage table is on, but the QPs are those without a map), and the map's
 writer (nmpc_batch_stage_limits_from_map) is timed alone: node_cycle_map_ms, node_cycle_open_map_ms and writer_ms next
-to the figures without a map.
+to the figures without a map. With --dump-failed OUT.npz as well: no timings; the B = 1024, all-active handle with the seeded map
+runs one node_cycle at a time with host copies of what each solve reads, stops at the first nonzero solver status and
+writes that robot's whole history since its cold start to OUT.npz (tests/golden/make_saturated_fixture.md).
 
 Poses of --nearest and --tick: the path points at the seeded nearest_u, displaced by a seeded offset of up to 0.1 m.
 
 usage: python tools/bench_path.py [--B 4096] [--num-poses 41] [--iters 50] [--nearest | --tick | --node | --mission |
-                                                                                     --cycle [--speed-map]]
+                                                                                     --cycle [--speed-map
+                                                                                     [--dump-failed OUT.npz]]]
 """
 import argparse
 import json
@@ -138,7 +141,13 @@ def main(argv=None):
     ap.add_argument("--mission", action="store_true")
     ap.add_argument("--cycle", action="store_true")
     ap.add_argument("--speed-map", action="store_true", help="with --cycle: node_cycle with a speed map attached too")
+    ap.add_argument("--dump-failed", metavar="OUT.npz", help="with --cycle --speed-map: no timings; run the B = 1024 "
+                    "all-active map handle tick by tick and write the first failing robot's history")
     a = ap.parse_args(argv)
+    if a.dump_failed:
+        if not (a.cycle and a.speed_map):
+            ap.error("--dump-failed needs --cycle --speed-map")
+        return dump_failed(a)
     if a.cycle:
         return cycle_bench(a)
     if a.mission:
@@ -430,6 +439,88 @@ def cycle_bench(a):
                 invalid=int((buf["valid"] == 0).sum()), cycle_equals_tick=bool(same),
                 dropped=int((cyc["M"].cpu() != t(mode).cpu()).sum()),
                 failed=dict(cycle=int((cyc["st"] != 0).sum()), tick=int((tick["st"] != 0).sum())))), flush=True)
+
+
+def dump_failed(a, B=1024, max_ticks=165):
+    """cycle_bench's B = 1024, all-active handle with the seeded speed map, one node_cycle at a time (165 ticks at the
+    most: what three rounds of 5 + 50 calls are). Before each cycle: the iterate and the carried refs of the fleet, and
+    the limits the map's writer gives on them (the cycle's own writer runs on the same inputs; the table's bytes are
+    compared after the cycle). After it: the references the gate made and the solve's outputs. At the first nonzero
+    status the robot's history goes to a.dump_failed, float32, and one JSON line says what was found."""
+    from nmpc_nav_control_amd._lib import NODE_FOLLOW_PATH, NODE_GOTO_POSE
+    from nmpc_nav_control_amd.batch import BatchSolver, NodeInput, NodeParams, SpeedMap
+    dev = torch.device("cuda:0")
+    N = a.num_poses - 1
+    npar = NodeParams.default()
+    i32, f64, now, period = torch.int32, torch.float64, 1700000000000000000, 25000000
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    rng = np.random.default_rng(20250826)
+    grid = rng.uniform(0.15, 1.0, (256, 256)).astype(np.float32)
+    grid[rng.uniform(size=grid.shape) < 0.2] = np.inf
+    smap = SpeedMap(-32.0, -32.0, 0.25, t(grid))
+    segs, nseg, nu = seeded_paths(B)
+    pose = seeded_poses(segs, nseg, nu).astype(np.float64)
+    rng = np.random.default_rng(B)
+    ang, r = rng.uniform(-math.pi, math.pi, B), rng.uniform(0.3, 1.0, B)
+    goal = np.stack([pose[0] + r * np.cos(ang), pose[1] + r * np.sin(ang), pose[2] + rng.uniform(0.2, 1.0, B)])
+    act = np.sort(rng.permutation(B))
+    mode = np.zeros(B, np.uint8)
+    mode[act[0::2]] = NODE_FOLLOW_PATH
+    mode[act[1::2]] = NODE_GOTO_POSE
+    s = BatchSolver("diff", N, B, device=dev)
+    S, NS, M, G = t(segs), t(nseg), t(mode), t(goal)
+    U = torch.zeros(B, dtype=f64, device=dev)
+    stamp, smp = t(np.full(B, now - 2000000, np.int64)), t(pose)
+    s.enable_input(4)
+    s.push_samples(stamp - period, smp)
+    s.push_samples(stamp, smp)
+    s.set_speed_map(smap)
+    nin = NodeInput.default(now_ns=now, pose=torch.zeros(3, B, device=dev), vel=torch.zeros(3, B, device=dev),
+                            valid=torch.zeros(B, dtype=torch.uint8, device=dev))
+    fresh = torch.ones(B, dtype=torch.uint8, device=dev)
+    out = dict(cmd=torch.zeros(3, B, device=dev), u0=torch.zeros(2, B, device=dev),
+               status=torch.zeros(B, dtype=i32, device=dev), qp_iter=torch.zeros(B, dtype=i32, device=dev),
+               qp_res=torch.zeros(3, B, device=dev))
+    traj = torch.zeros(N + 1, 3, B, device=dev)
+    vlim = torch.zeros(N + 1, B, device=dev)
+    s.node_input(nin, M, goal_map=G)  # (the stage's outputs for the first writer call below: the samples are fixed)
+    torch.cuda.synchronize()
+    hist, same_table = [], True
+    host = lambda x: x.cpu().numpy().copy()  # noqa: E731
+    for tick in range(max_ticks):
+        xb, ub, cr = (v.to_tensor()[:, :B] for v in s.state())
+        s.stage_limits_from_map(smap, pose=nin.pose, reset=fresh, vlim=vlim)
+        torch.cuda.synchronize()
+        rec = dict(xbar=host(xb), ubar=host(ub), carried=host(cr), vlim=host(vlim), reset=host(fresh), mode=host(M))
+        table = s.stage_bounds().to_tensor()
+        s.node_cycle(npar, nin, M, goal_map=G, segs=S, nseg=NS, path_u=U, reset=fresh, traj_out=traj, **out)
+        torch.cuda.synchronize()
+        # (the rows of a robot that left GOTO_POSE / FOLLOW_PATH in this cycle are not rewritten: none has, before a failure)
+        same_table &= bool(torch.equal(table, s.stage_bounds().to_tensor()))
+        rec.update(traj=host(traj), pose=host(nin.pose), vel=host(nin.vel), **{k: host(v) for k, v in out.items()})
+        hist.append(rec)
+        bad = np.flatnonzero(rec["status"] != 0)
+        if len(bad):
+            break
+    else:
+        print(json.dumps(dict(metric="first failed solve (diff N=%d, B=%d, seeded speed map)" % (N, B), failed=False,
+                              ticks=max_ticks, table_equals_writer=same_table)), flush=True)
+        return
+    i = int(bad[0])
+    col = lambda k: np.stack([h[k][..., i] for h in hist]).astype(np.float32)  # noqa: E731
+    np.savez_compressed(
+        a.dump_failed, robot=i, tick=tick, N=N, mode=np.array([h["mode"][i] for h in hist], np.uint8),
+        reset=np.array([h["reset"][i] for h in hist], np.uint8), pose=col("pose"), vel=col("vel"),
+        goal=goal[:, i].astype(np.float32), traj=col("traj"), vlim=col("vlim"), carried=col("carried"),
+        xbar=col("xbar"), ubar=col("ubar"), u0=col("u0"), cmd=col("cmd"), qp_res=col("qp_res"),
+        status=np.array([h["status"][i] for h in hist], np.int32),
+        qp_iter=np.array([h["qp_iter"][i] for h in hist], np.int32))
+    plan = s.plan_ex(B, "run")
+    print(json.dumps(dict(metric="first failed solve (diff N=%d, B=%d, seeded speed map)" % (N, B), failed=True,
+                          robot=i, tick=tick, status=int(hist[-1]["status"][i]), qp_iter=int(hist[-1]["qp_iter"][i]),
+                          qp_res=[float(x) for x in hist[-1]["qp_res"][:, i]], mode=int(hist[-1]["mode"][i]),
+                          failed_robots=[int(b) for b in bad], table_equals_writer=same_table,
+                          kernel=plan["kernel"], segments=plan["segments"], out=a.dump_failed)), flush=True)
 
 
 def mission_sets(segs, nseg):
