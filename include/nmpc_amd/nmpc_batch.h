@@ -686,10 +686,11 @@ int nmpc_batch_set_speed_map(nmpc_batch* b, const nmpc_speed_map* map, const nmp
  * a standing robot (h = 0) has no direction and counts every track in range.
  * The caller's duties are the speed map's, and: the tracks are configuration, not state: checkpoints carry the stage
  * table, not the tracks; the buffer stays the caller's device memory and must outlive its use.
- * Out of scope: this is speed limiting, not collision avoidance: two robots head-on both come down to v_floor and
- * keep creeping. No general constraints in the QP, no change to the solve kernels, no per-track radii (a caller with
- * mixed vehicle sizes takes the largest clearance), no rotated footprints, not the capsule ABI, not
- * nmpc_batch_solve_iterate's caller-held iterate, no spatial index over the map.
+ * Out of scope: this is speed limiting, not collision avoidance: by this rule alone two robots head-on both come down
+ * to v_floor and keep creeping; with the separation guard below attached they stop at stop_gap and stay held until
+ * one of them is given another path. No general constraints in the QP, no change to the solve kernels, no per-track
+ * radii (a caller with mixed vehicle sizes takes the largest clearance), no rotated footprints, not the capsule ABI,
+ * not nmpc_batch_solve_iterate's caller-held iterate, no spatial index over the map.
  * Argument errors (NMPC_ERR_ARG): B out of range, tracks NULL, M < 0, K < 0, xy NULL with M > 0, own_first < -1,
  * own_first >= 0 && own_first + B > M, gain not finite or <= 0, clearance not finite or < 0, range not finite or
  * <= clearance, the speed map's payload checks when map is given and the speed rule's when rule is given, reset
@@ -734,6 +735,97 @@ int nmpc_batch_stage_limits_from_tracks(nmpc_batch* b, int B, const nmpc_tracks*
  * nothing attached, the cycle enqueues exactly the launches it enqueued without this interface. */
 int nmpc_batch_set_tracks(nmpc_batch* b, const nmpc_tracks* tracks, const nmpc_sep_rule* sep /* NULL: defaults */,
                           int export_own);
+
+/* The separation guard: right of way and a protective hold on top of the rule above. The rule is a scanner's warning
+ * field: it slows a robot down and, because a speed box must keep an interior (v_floor > 0), can never stop it. The
+ * guard adds the protective field, which stops a robot that is too close to anything, and a priority filter, which lets
+ * one robot of a crossing pair drive on. Neither reaches the solve kernels or the gate's kernels.
+ * Right of way. With priority given, a pair (robot i, track j) that counts under the rule must also have
+ * priority[j] >= own_i to enter the minimum the speed cap is made from:
+ *   own_i  = own_priority[i], or priority[own_first + i] when own_priority is NULL
+ *   qa_k   the rule's q_k: the minimum over every counting pair
+ *   qy_k   the minimum over the counting pairs with priority[j] >= own_i; with priority NULL, qy_k == qa_k
+ *   gap_k  = sqrtf(qy_k) feeds s_k, z_k, r_k and lim_k exactly as in the rule; gap[k*B + i] = gap_k
+ *   gapa_k = sqrtf(qa_k) feeds the hold only; gap_all[k*B + i] = gapa_k when given
+ * Larger wins; equal priorities both count (today's behaviour). A track that must always count -- a person, a pallet,
+ * a robot outside the scheme -- gets INT_MAX: that is the caller's duty. Priorities are meant for crossings. In one
+ * lane a high-priority follower behind a low-priority leader is not slowed by the leader and ends in a hold behind
+ * it; a caller who does not want that gives a convoy one priority.
+ * Standing robots. A robot with held[i] != 0 on entry takes pose[0..1][i] as its position at every stage, as a reset
+ * robot does: it stands. It keeps the iterate's direction h_k, which a reset robot (h_k = 0) does not have; so
+ * "stands" is reset || held and "has no direction" is reset. The map lookup of a held robot stays at its iterate's
+ * positions, the linearisation points its boxes apply to.
+ * The hold, for a robot whose mode is GOTO_POSE or FOLLOW_PATH (every robot when mode is NULL):
+ *   m      = min over k = 0..min(hold_stages, N) of gapa_k (fminf; +inf when nothing counts; a NaN never counts)
+ *   held'  = reset[i] ? 0 : (held ? m < release_gap : m < stop_gap)
+ * A robot in any other mode gets held' = 0, and with hold == 0 every robot does. A reset robot is never held: it has no
+ * prediction and no direction, so it counts every track in range, behind it too; once held it would never solve, never
+ * get a direction and never be released. It solves once under the writer's cap and is judged from the next cycle on.
+ * The hold never writes reset (in the fp64 closed loop every solve of a released robot succeeds). One duty comes with
+ * it: a held robot's carried refs stay at what they were when it was held (forwards, at least v_floor) while the robot
+ * stands, so a prediction that starts from them still moves forwards for a stage or two. A robot released by the
+ * hysteresis has room for that. A caller that gives a held robot a new target to get it out of a deadlock zeroes its
+ * carried speed refs (nmpc_batch_state) along with setting reset; otherwise the hold takes the robot again in the cycle
+ * after the reset one. The speed refs are the rows c is taken from: all NBX rows of carried for diff and omni4, row 0
+ * (v_ref) for tric, whose row 1 (alpha_ref) stays.
+ * held is one byte per robot, owned by the handle, 0 at first. Unlike the tracks and the guard, which are
+ * configuration, it is state: a checkpoint carries it (nmpc_batch_sep_state) next to the stage table.
+ * Out of scope: deadlock resolution (a head-on pair stays held and reports HELD every cycle; replanning is the fleet
+ * manager's), priorities that depend on geometry, per-track radii and footprints, the capsule ABI,
+ * nmpc_batch_solve_iterate's caller-held iterate, a spatial index, and any change to the solve kernels or the gate's.
+ * Argument errors (NMPC_ERR_ARG), on top of the writer's: stop_gap not finite or <= 0, release_gap not finite,
+ * < stop_gap or > the rule's range, hold_stages < 0, priority given with own_priority NULL and own_first < 0, a
+ * guard without pose (a held robot stands at it), gap_all without a guard,
+ * nmpc_batch_sep_hold before any nmpc_batch_stage_limits_from_tracks_ex call with a guard on the handle. */
+#define NMPC_NODE_EV_HELD (9) /* protective hold: stop command, the mode stays, the robot did not tick */
+
+typedef struct nmpc_sep_guard {
+    const int* priority;     /* [M] device or NULL: right of way of every track; larger wins; equal: both count */
+    const int* own_priority; /* [B] device or NULL: NULL reads priority[own_first + i] (needs own_first >= 0) */
+    float stop_gap;          /* m, > 0: hold below this centre distance (default 0.45) */
+    float release_gap;       /* m, >= stop_gap, <= the rule's range: a held robot is released at or above it
+                                (default 0.55) */
+    int hold_stages;         /* >= 0: the stages 0..min(hold_stages, N) form the protective field (default 4) */
+    int hold;                /* default 1; 0: right of way only, nobody is held */
+} nmpc_sep_guard;
+int nmpc_sep_guard_default(nmpc_sep_guard* g);
+/* nmpc_batch_stage_limits_from_tracks plus the guard (NULL: exactly that call) and gap_all. With a guard the call
+ * reads the handle's held and leaves the qa plane on the handle for nmpc_batch_sep_hold. */
+int nmpc_batch_stage_limits_from_tracks_ex(nmpc_batch* b, int B, const nmpc_tracks* tracks,
+                                           const nmpc_sep_rule* sep /* NULL: defaults */,
+                                           const nmpc_sep_guard* guard /* or NULL */,
+                                           const nmpc_speed_map* map /* or NULL */,
+                                           const nmpc_speed_rule* rule /* NULL: defaults */, const float* pose,
+                                           const unsigned char* reset, const unsigned char* mask,
+                                           float* vlim /* [N+1][B] or NULL */, float* gap /* [N+1][B] or NULL */,
+                                           float* gap_all /* [N+1][B] or NULL */, void* stream);
+/* The hold: one small launch, one lane per robot, on the qa plane the preceding _ex writer call left (the same B; a
+ * robot the writer did not process has a stale plane). It updates the handle's held for the robots [0, B), writes
+ * held_out [B] when given, and does nothing else: a caller of the plain ticks acts on held_out itself. mode [B] or
+ * NULL (every robot is judged), reset [B] or NULL; all device. Only stop_gap, release_gap, hold_stages and hold of the
+ * guard are read, and release_gap's upper bound is the writer call's to check. */
+int nmpc_batch_sep_hold(nmpc_batch* b, int B, const nmpc_sep_guard* guard, const unsigned char* mode,
+                        const unsigned char* reset, unsigned char* held_out /* [B] or NULL */, void* stream);
+/* Attach (a copy of the struct; the priority arrays stay the caller's device memory) or detach (NULL) the guard. Both
+ * clear held. While a guard and tracks are attached, nmpc_batch_node_cycle runs between the input stage and the tick:
+ * (1) the export with export_own, in which a robot held on entry is a standing obstacle at its pose, like a reset one;
+ * (2) the _ex writer; (3) the hold. A robot with held' != 0 then does not tick: it gets a stop command (zero cmd, u0,
+ * status, qp_iter, qp_res: the values of a robot that does not solve; err and traj_out NaN), keeps the mode it had, so
+ * that it resumes by itself, and reports NMPC_NODE_EV_HELD; its reset flag, iterate, carried refs, warm flag, records,
+ * placement key, path window, remains and path_u stay bit for bit, and n_solved does not count it. (It is parked in
+ * IDLE before the gate, whose kernels are unchanged, and its mode comes back after the tick from the handle's scratch;
+ * under strict an invalid robot is ERROR before the hold and is not held; without strict an invalid held robot gets its
+ * mode back and then goes to ERROR by the cycle's rule. If the cycle returns an error after the hold's launch was
+ * queued -- a failed allocation or launch in the tick -- the status launch does not run and a held robot's entry of the
+ * caller's mode array stays IDLE: after an error from the cycle the caller writes its modes again, as it has to after
+ * any error in the middle of a cycle.) A guard without tracks attached is inert. With no guard
+ * attached the cycle enqueues exactly the launches it enqueued without this interface and allocates nothing. */
+int nmpc_batch_set_sep_guard(nmpc_batch* b, const nmpc_sep_guard* guard);
+/* The hold's state for checkpoints: *held [capacity] device bytes, zeros at first. The call allocates the guard's
+ * scratch if no call has needed it yet: held, the qa plane [N+1][capacity] and the cycle's two save arrays come in one
+ * piece. nmpc_batch_export_tracks has no held operand: a caller of the plain ticks who wants a held robot exported as a
+ * standing obstacle, as the cycle does, passes reset | held as the export's reset. */
+int nmpc_batch_sep_state(nmpc_batch* b, unsigned char** held);
 
 /* Per-robot model parameters. A fleet of one model family mixes vehicles: two wheelbases of the same differential
  * base, loaded and empty trucks whose tau_v differ by a factor of two or three (the reference runs one node per robot,

@@ -114,12 +114,19 @@ class SepRuleStruct(ctypes.Structure):
                 ("ahead_only", ctypes.c_int)]
 
 
+class SepGuardStruct(ctypes.Structure):
+    """Mirror of nmpc_sep_guard (include/nmpc_amd/nmpc_batch.h): priority [M] and own_priority [B] device pointers."""
+    _fields_ = [("priority", c_void_p), ("own_priority", c_void_p), ("stop_gap", ctypes.c_float),
+                ("release_gap", ctypes.c_float), ("hold_stages", ctypes.c_int), ("hold", ctypes.c_int)]
+
+
 # NMPC_NODE_* (a robot's state in the node's state machine) and NMPC_NODE_EV_* (what the tick did for it)
 NODE_IDLE, NODE_GOTO_POSE, NODE_FOLLOW_PATH, NODE_BREAK, NODE_ERROR = 0, 1, 2, 3, 4
 (NODE_EV_NONE, NODE_EV_SOLVED, NODE_EV_ARRIVED, NODE_EV_GOAL_TOO_FAR, NODE_EV_OFF_PATH, NODE_EV_SOLVE_FAILED,
  NODE_EV_BREAK) = range(7)
 NODE_EV_NEXT_PART = 7  # nmpc_batch_node_tick_queue only
 NODE_EV_INPUT_INVALID = 8  # nmpc_batch_node_cycle with strict = 1 only
+NODE_EV_HELD = 9  # nmpc_batch_node_cycle with a separation guard attached only
 
 
 class CodegenDesc(ctypes.Structure):
@@ -157,6 +164,8 @@ BATCH_SYMBOLS = [
     "nmpc_batch_set_speed_map",
     "nmpc_tracks_default", "nmpc_sep_rule_default", "nmpc_batch_export_tracks",
     "nmpc_batch_stage_limits_from_tracks", "nmpc_batch_set_tracks",
+    "nmpc_sep_guard_default", "nmpc_batch_stage_limits_from_tracks_ex", "nmpc_batch_sep_hold",
+    "nmpc_batch_set_sep_guard", "nmpc_batch_sep_state",
     "nmpc_batch_set_robot_model", "nmpc_batch_robot_model", "nmpc_batch_clear_robot_model",
     "nmpc_batch_set_robot_frame", "nmpc_batch_recentre", "nmpc_batch_to_frame", "nmpc_batch_from_frame",
     "nmpc_batch_robot_frame", "nmpc_batch_clear_robot_frame",
@@ -258,6 +267,12 @@ def lib():
     L.nmpc_batch_export_tracks.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, vp]
     L.nmpc_batch_stage_limits_from_tracks.argtypes = [vp, i, TR, SP, SM, SR, vp, vp, vp, vp, vp, vp]
     L.nmpc_batch_set_tracks.argtypes = [vp, TR, SP, i]
+    SG = ctypes.POINTER(SepGuardStruct)
+    L.nmpc_sep_guard_default.argtypes = [SG]
+    L.nmpc_batch_stage_limits_from_tracks_ex.argtypes = [vp, i, TR, SP, SG, SM, SR, vp, vp, vp, vp, vp, vp, vp]
+    L.nmpc_batch_sep_hold.argtypes = [vp, i, SG, vp, vp, vp, vp]
+    L.nmpc_batch_set_sep_guard.argtypes = [vp, SG]
+    L.nmpc_batch_sep_state.argtypes = [vp, ctypes.POINTER(vp)]
     L.nmpc_batch_set_robot_model.argtypes = [vp, i, vp, vp, vp]
     L.nmpc_batch_robot_model.argtypes = [vp, ctypes.POINTER(vp), c_int_p, c_int_p]
     L.nmpc_batch_clear_robot_model.argtypes = [vp]

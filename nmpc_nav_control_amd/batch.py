@@ -9,8 +9,9 @@ import ctypes
 import torch
 
 from ._lib import (KERNELS, MODEL_IDS, PLAN_MODES, REC_LAYOUTS, SCHEDULES, FleetRenew, FleetStats, LaunchPlan,
-                   ModelParams, NodeInputStruct, NodeParamsStruct, RobotParamsStruct, SepRuleStruct, SpeedMapStruct,
-                   SpeedRuleStruct, StageBoundsStruct, TracksStruct, check, default_params, lib, model_dims)
+                   ModelParams, NodeInputStruct, NodeParamsStruct, RobotParamsStruct, SepGuardStruct, SepRuleStruct,
+                   SpeedMapStruct, SpeedRuleStruct, StageBoundsStruct, TracksStruct, check, default_params, lib,
+                   model_dims)
 
 
 def _ptr(t, dtype=None, shape=None, name="argument"):
@@ -140,6 +141,26 @@ class Tracks:
                               own_first=int(own_first))
 
 
+class SepGuard:
+    """nmpc_sep_guard (include/nmpc_amd/nmpc_batch.h): right of way and the protective hold on top of the separation
+    rule. priority int32 [M] device or None (larger wins, equal: both count; INT_MAX for what must always count),
+    own_priority int32 [B] device or None (then priority[own_first + i]); this object keeps both alive. A robot is held
+    when the smallest unfiltered gap over the stages 0..min(hold_stages, N) is below stop_gap and released at or above
+    release_gap; hold=0: right of way only."""
+
+    def __init__(self, priority=None, own_priority=None, stop_gap=0.45, release_gap=0.55, hold_stages=4, hold=1):
+        self.priority, self.own_priority = priority, own_priority
+        I32 = torch.int32
+        for name, a in (("priority", priority), ("own_priority", own_priority)):
+            if a is not None and a.dim() != 1:
+                raise ValueError(f"{name}: expected a device tensor int32 [M] (priority) or [B] (own_priority)")
+        self.c = SepGuardStruct(
+            priority=_ptr(priority, I32, tuple(priority.shape), "priority") if priority is not None else None,
+            own_priority=_ptr(own_priority, I32, tuple(own_priority.shape), "own_priority")
+            if own_priority is not None else None,
+            stop_gap=float(stop_gap), release_gap=float(release_gap), hold_stages=int(hold_stages), hold=int(hold))
+
+
 def _sep_rule(clearance, gain, range, ahead_only):
     return SepRuleStruct(clearance=float(clearance), gain=float(gain), range=float(range), ahead_only=int(ahead_only))
 
@@ -172,6 +193,7 @@ class BatchSolver:
         self._h = ctypes.c_void_p()
         self._speed_map = None  # the attached SpeedMap (set_speed_map): its grid is the library's to read
         self._tracks = None     # the attached Tracks (set_tracks): likewise its buffer
+        self._sep_guard = None  # the attached SepGuard (set_sep_guard): likewise its priorities
         with torch.cuda.device(self.device):
             check(lib().nmpc_batch_create(ctypes.byref(self.params), self.capacity, ctypes.byref(self._h)),
                   "nmpc_batch_create")
@@ -382,20 +404,36 @@ class BatchSolver:
 
     def stage_limits_from_tracks(self, tracks, map=None, pose=None, reset=None, mask=None, vlim=None, gap=None,
                                  clearance=0.6, gain=1.0, range=3.0, ahead_only=1, slope=0.8, v_floor=0.05, B=None,
-                                 stream=None):
+                                 stream=None, guard=None, gap_all=None):
         """The speed rows of the stage table from Tracks and, optionally, a SpeedMap
         (nmpc_batch_stage_limits_from_tracks): every stage of every processed robot's horizon gets the cap
         gain * (gap - clearance) from the gap to the nearest track within range at the same time (ahead_only: in the
         half plane of its direction of travel), and the speed map's rule makes a limit profile of the caps. pose, reset,
         mask, vlim, slope, v_floor as stage_limits_from_map; gap float32 [N+1][B] receives the gaps (+inf: no track
-        counts)."""
+        counts). guard: a SepGuard (nmpc_batch_stage_limits_from_tracks_ex): gap is then the gap to the nearest track
+        the robot gives way to, gap_all float32 [N+1][B] receives the unfiltered one, a robot that is held (sep_state)
+        stands at its pose, and sep_hold may follow."""
         if reset is not None and pose is None:
             raise ValueError("stage_limits_from_tracks: reset needs pose")
+        if gap_all is not None and guard is None:
+            raise ValueError("stage_limits_from_tracks: gap_all needs a guard")
+        if guard is not None and guard.priority is not None and guard.priority.numel() != tracks.M:
+            raise ValueError(f"guard: priority has {guard.priority.numel()} entries, the tracks are {tracks.M}")
         if B is None:
             given = [(pose, 1), (reset, 0), (mask, 0), (vlim, 1), (gap, 1)]
             B = next((self._batch_of(t, ax) for t, ax in given if t is not None), self.capacity)
         B = int(B)
         sep, rule = _sep_rule(clearance, gain, range, ahead_only), _speed_rule(slope, v_floor)
+        if guard is not None and guard.own_priority is not None and guard.own_priority.numel() < B:
+            raise ValueError(f"guard: own_priority has {guard.own_priority.numel()} entries, the call has {B} robots")
+        if guard is not None:
+            check(lib().nmpc_batch_stage_limits_from_tracks_ex(
+                self._h, B, ctypes.byref(tracks.c), ctypes.byref(sep), ctypes.byref(guard.c),
+                ctypes.byref(map.c) if map is not None else None, ctypes.byref(rule), _ptr(pose, F32, (3, B), "pose"),
+                _ptr(reset, U8, (B,), "reset"), _ptr(mask, U8, (B,), "mask"), _ptr(vlim, F32, (self.N + 1, B), "vlim"),
+                _ptr(gap, F32, (self.N + 1, B), "gap"), _ptr(gap_all, F32, (self.N + 1, B), "gap_all"),
+                _stream(stream)), "nmpc_batch_stage_limits_from_tracks_ex")
+            return
         check(lib().nmpc_batch_stage_limits_from_tracks(
             self._h, B, ctypes.byref(tracks.c), ctypes.byref(sep), ctypes.byref(map.c) if map is not None else None,
             ctypes.byref(rule), _ptr(pose, F32, (3, B), "pose"), _ptr(reset, U8, (B,), "reset"),
@@ -414,6 +452,35 @@ class BatchSolver:
             check(lib().nmpc_batch_set_tracks(self._h, ctypes.byref(tracks.c), ctypes.byref(sep), int(bool(export_own))),
                   "nmpc_batch_set_tracks")
         self._tracks = tracks
+
+    def sep_hold(self, guard, mode=None, reset=None, held_out=None, B=None, stream=None):
+        """The protective hold (nmpc_batch_sep_hold): one launch on what the preceding stage_limits_from_tracks call
+        with a guard left on the handle; updates the handle's held (sep_state) and writes held_out uint8 [B] when
+        given. mode uint8 [B] or None (every robot is judged), reset uint8 [B] or None."""
+        if B is None:
+            given = [(mode, 0), (reset, 0), (held_out, 0)]
+            B = next((self._batch_of(t, ax) for t, ax in given if t is not None), self.capacity)
+        B = int(B)
+        check(lib().nmpc_batch_sep_hold(self._h, B, ctypes.byref(guard.c), _ptr(mode, U8, (B,), "mode"),
+                                        _ptr(reset, U8, (B,), "reset"), _ptr(held_out, U8, (B,), "held_out"),
+                                        _stream(stream)), "nmpc_batch_sep_hold")
+
+    def set_sep_guard(self, guard):
+        """Attach a SepGuard to the solver, or detach it (None) (nmpc_batch_set_sep_guard); either way held is cleared.
+        While a guard and tracks are attached, node_cycle runs the export, the guarded writer and the hold, and a held
+        robot does not tick: stop command, its mode stays, event NMPC_NODE_EV_HELD."""
+        if guard is not None and guard.priority is not None and self._tracks is not None \
+                and guard.priority.numel() != self._tracks.M:
+            raise ValueError(f"guard: priority has {guard.priority.numel()} entries, the tracks are {self._tracks.M}")
+        check(lib().nmpc_batch_set_sep_guard(self._h, ctypes.byref(guard.c) if guard is not None else None),
+              "nmpc_batch_set_sep_guard")
+        self._sep_guard = guard
+
+    def sep_state(self):
+        """View of the hold's state (nmpc_batch_sep_state): held [1][cap] (uint8). State, for checkpoints."""
+        h = ctypes.c_void_p()
+        check(lib().nmpc_batch_sep_state(self._h, ctypes.byref(h)), "nmpc_batch_sep_state")
+        return _DeviceView(h.value, (1, self.capacity), self.device, torch.uint8)
 
     def stage_bounds(self):
         """View of the stage table as opaque bytes [1][bytes] (uint8), or None while it is off
@@ -868,4 +935,4 @@ def _hip():
     return _hip_lib
 
 
-__all__ = ["BatchSolver", "ModelParams", "NodeInput", "NodeParams", "SpeedMap", "Tracks", "default_params"]
+__all__ = ["BatchSolver", "ModelParams", "NodeInput", "NodeParams", "SepGuard", "SpeedMap", "Tracks", "default_params"]

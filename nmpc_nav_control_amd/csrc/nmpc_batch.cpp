@@ -99,6 +99,14 @@ struct nmpc_batch {
     float* sep_q = nullptr;
     double* sep_boxes = nullptr;
     int sep_boxes_m = 0;
+    // the separation guard (nmpc_batch_set_sep_guard; sguard_on false: none attached) and its scratch, allocated by the
+    // first call that needs it: the qa plane [N+1][capacity] (sep_qa_ready: a guarded writer call has filled it), the
+    // hold's state held [capacity], and the cycle's saved modes and remains [capacity] of the parked robots
+    nmpc_sep_guard sguard{};
+    bool sguard_on = false, sep_qa_ready = false;
+    float* sep_qa = nullptr;
+    unsigned char *sep_held = nullptr, *sep_mode_save = nullptr;
+    double* sep_remains_save = nullptr;
 };
 
 namespace {
@@ -516,6 +524,32 @@ const char* bad_tracks(const nmpc_tracks* t, const nmpc_sep_rule* r, int B)
     return nullptr;
 }
 
+nmpc_sep_guard sep_guard_default()
+{
+    nmpc_sep_guard g;
+    std::memset(&g, 0, sizeof(g));
+    g.stop_gap = 0.45f;
+    g.release_gap = 0.55f;
+    g.hold_stages = 4;
+    g.hold = 1;
+    return g;
+}
+
+// the guard's payload check: the failed check, or nullptr (g may be NULL: no guard). range < 0: not known to the call
+// (nmpc_batch_sep_hold), release_gap's upper bound is the writer's; own_first < -1: likewise not known
+const char* bad_guard(const nmpc_sep_guard* g, float range, int own_first)
+{
+    if (!g) return nullptr;
+    if (!std::isfinite(g->stop_gap) || !(g->stop_gap > 0.0f)) return "separation guard: stop_gap must be finite and > 0";
+    if (!std::isfinite(g->release_gap) || !(g->release_gap >= g->stop_gap))
+        return "separation guard: release_gap must be finite and >= stop_gap";
+    if (range >= 0.0f && !(g->release_gap <= range)) return "separation guard: release_gap must be <= range";
+    if (g->hold_stages < 0) return "separation guard: hold_stages must be >= 0";
+    if (g->priority && !g->own_priority && own_first == -1)
+        return "separation guard: priority without own_priority needs own_first >= 0";
+    return nullptr;
+}
+
 // the speed map's writer launch on the stage table (which is ready): its arguments from the handle's tables and state
 // (map nullptr and sep given: fleet separation without a map; sep: the q plane is ready on the stream)
 hipError_t speed_map_write(nmpc_batch* b, int B, const nmpc_speed_map* map, const nmpc_speed_rule& rule,
@@ -548,7 +582,7 @@ hipError_t speed_map_write(nmpc_batch* b, int B, const nmpc_speed_map* map, cons
     a.mode = mode;
     a.vlim = vlim;
     if (sep) {
-        a.sep_q = b->sep_q;
+        a.sep_q = b->sep_q;  // (with a guard: the qy plane)
         a.sep_gain = sep->gain;
         a.sep_clearance = sep->clearance;
         a.gap = gap;
@@ -575,8 +609,46 @@ int sep_scratch(nmpc_batch* b, int M)
     return NMPC_OK;
 }
 
+// the guard's scratch (see the handle): everything at once, held zeroed, the qa plane +inf
+int guard_scratch(nmpc_batch* b)
+{
+    if (b->sep_held) return NMPC_OK;
+    const size_t S = (size_t)b->capacity, n = (size_t)(b->prm.N + 1) * S;
+    float* qa = nullptr;
+    unsigned char *held = nullptr, *ms = nullptr;
+    double* rs = nullptr;
+    const float inf = INFINITY;
+    int bits;
+    std::memcpy(&bits, &inf, sizeof(bits));
+    hipError_t e;
+    if ((e = hipMalloc(&qa, sizeof(float) * n)) != hipSuccess || (e = hipMalloc(&held, S)) != hipSuccess ||
+        (e = hipMalloc(&ms, S)) != hipSuccess || (e = hipMalloc(&rs, sizeof(double) * S)) != hipSuccess ||
+        (e = hipMemsetD32((hipDeviceptr_t)qa, bits, n)) != hipSuccess || (e = hipMemset(held, 0, S)) != hipSuccess ||
+        (e = hipMemset(ms, 0, S)) != hipSuccess || (e = hipMemset(rs, 0, sizeof(double) * S)) != hipSuccess ||
+        (e = hipStreamSynchronize(nullptr)) != hipSuccess) {
+        for (void* p : {(void*)qa, (void*)held, (void*)ms, (void*)rs}) (void)hipFree(p);
+        return hip_err(e, "hipMalloc");
+    }
+    b->sep_qa = qa;
+    b->sep_held = held;
+    b->sep_mode_save = ms;
+    b->sep_remains_save = rs;
+    return NMPC_OK;
+}
+
+// held = 0 for every robot (attach and detach of the guard); nothing to do before the scratch exists
+int guard_clear_held(nmpc_batch* b)
+{
+    if (!b->sep_held) return NMPC_OK;
+    hipError_t e = hipDeviceSynchronize();  // (launches that read or write held on any stream)
+    if (e == hipSuccess) e = hipMemset(b->sep_held, 0, (size_t)b->capacity);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    return hip_err(e, "hipMemset");
+}
+
 hipError_t export_tracks(nmpc_batch* b, int B, const float* pose, const unsigned char* reset,
-                         const unsigned char* mode, double* xy, int M, int K, int first, hipStream_t s)
+                         const unsigned char* mode, double* xy, int M, int K, int first, hipStream_t s,
+                         const unsigned char* held = nullptr)
 {
     ExportTracksArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -589,6 +661,7 @@ hipError_t export_tracks(nmpc_batch* b, int B, const float* pose, const unsigned
     a.pose = pose;
     a.reset = reset;
     a.mode = mode;
+    a.held = held;
     a.xy = xy;
     a.M = M;
     a.K = K;
@@ -596,10 +669,37 @@ hipError_t export_tracks(nmpc_batch* b, int B, const float* pose, const unsigned
     return launch_export_tracks(a, s);
 }
 
-// fleet separation's writer on the stage table and the scratch (both ready): the q plane, then the rule's launch
+// the hold's launch on the qa plane (ready). mode_rw: the cycle's mode array, whose held robots are parked in IDLE
+hipError_t sep_hold(nmpc_batch* b, int B, const nmpc_sep_guard& g, const unsigned char* mode, const unsigned char* reset,
+                    unsigned char* held_out, unsigned char* mode_rw, const double* remains, hipStream_t s)
+{
+    SepHoldArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.N = b->prm.N;
+    a.cap = b->capacity;
+    a.qa = b->sep_qa;
+    a.last = g.hold_stages < b->prm.N ? g.hold_stages : b->prm.N;
+    a.stop_gap = g.stop_gap;
+    a.release_gap = g.release_gap;
+    a.hold = g.hold ? 1 : 0;
+    a.mode = mode;
+    a.reset = reset;
+    a.held = b->sep_held;
+    a.held_out = held_out;
+    a.mode_rw = mode_rw;
+    a.mode_save = b->sep_mode_save;
+    a.remains = remains;
+    a.remains_save = b->sep_remains_save;
+    return launch_sep_hold(a, s);
+}
+
+// fleet separation's writer on the stage table and the scratch (both ready): the q plane, then the rule's launch.
+// guard: the guard form (its scratch is ready too): q is qy, the qa plane is written, gap_all takes its square roots
 hipError_t tracks_write(nmpc_batch* b, int B, const nmpc_tracks& t, const nmpc_sep_rule& sep, const nmpc_speed_map* map,
                         const nmpc_speed_rule& rule, const float* pose, const unsigned char* reset,
-                        const unsigned char* mask, const unsigned char* mode, float* vlim, float* gap, hipStream_t s)
+                        const unsigned char* mask, const unsigned char* mode, float* vlim, float* gap, hipStream_t s,
+                        const nmpc_sep_guard* guard = nullptr, float* gap_all = nullptr)
 {
     SepArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -621,8 +721,17 @@ hipError_t tracks_write(nmpc_batch* b, int B, const nmpc_tracks& t, const nmpc_s
     a.cull2 = (double)a.range2 * (1.0 + 1e-5);  // separation.hip: why this is conservative
     a.boxes = b->sep_boxes;
     a.q = b->sep_q;
+    if (guard) {
+        a.guard = 1;
+        a.priority = guard->priority;
+        a.own_priority = guard->own_priority;
+        a.held = b->sep_held;
+        a.qa = b->sep_qa;
+        a.gap_all = gap_all;
+    }
     const hipError_t e = launch_sep_min(a, s);
     if (e != hipSuccess) return e;
+    if (guard) b->sep_qa_ready = true;
     return speed_map_write(b, B, map, rule, pose, reset, mask, mode, vlim, s, &sep, gap);
 }
 
@@ -876,7 +985,8 @@ int nmpc_batch_destroy(nmpc_batch* b)
     for (const DevTable* t : {&b->rparams, &b->sbounds, &b->rmodel, &b->rframe}) (void)hipFree(t->p);
     for (void* p : {(void*)b->in_st.stamp, (void*)b->in_st.sample, (void*)b->in_st.count, (void*)b->in_st.newest,
                     (void*)b->in_st.held, (void*)b->in_pose, (void*)b->in_vel, (void*)b->in_goal, (void*)b->in_steer,
-                    (void*)b->in_valid, (void*)b->sep_q, (void*)b->sep_boxes})
+                    (void*)b->in_valid, (void*)b->sep_q, (void*)b->sep_boxes, (void*)b->sep_qa, (void*)b->sep_held,
+                    (void*)b->sep_mode_save, (void*)b->sep_remains_save})
         (void)hipFree(p);
     delete b;
     return NMPC_OK;
@@ -1350,6 +1460,10 @@ int nmpc_batch_node_cycle(nmpc_batch* b, int B, const nmpc_node_params* np, cons
     if (!b->in_st.depth) return set_err(NMPC_ERR_ARG, "the input state is not enabled (nmpc_batch_enable_input)");
     if (b->trk_on && b->trk.own_first >= 0 && (long long)b->trk.own_first + B > b->trk.M)
         return set_err(NMPC_ERR_ARG, "tracks: own_first + B exceeds M");
+    const bool guarded = b->trk_on && b->sguard_on;  // (a guard without tracks is inert)
+    if (guarded) {
+        if (const char* bad = bad_guard(&b->sguard, b->seprule.range, b->trk.own_first)) return set_err(NMPC_ERR_ARG, bad);
+    }
     if (!go) return NMPC_OK;
     hipStream_t s = (hipStream_t)stream;
     nmpc_node_input r;
@@ -1359,16 +1473,23 @@ int nmpc_batch_node_cycle(nmpc_batch* b, int B, const nmpc_node_params* np, cons
     if (b->trk_on) {
         // fleet separation: the handle's own horizons into the track buffer, then the stage limits of the robots that
         // are about to solve from the tracks and, if one is attached, the speed map
+        // (a robot held on entry is exported as a standing obstacle at its pose)
         if (b->trk_export) {
             rc = hip_err(export_tracks(b, B, r.pose, reset, mode, const_cast<double*>(b->trk.xy), b->trk.M, b->trk.K,
-                                       b->trk.own_first, s), "export_tracks launch");
+                                       b->trk.own_first, s, guarded ? b->sep_held : nullptr), "export_tracks launch");
             if (rc) return rc;
         }
         if ((rc = sb_table(b, s)) || (rc = sep_scratch(b, b->trk.M))) return rc;
         rc = hip_err(tracks_write(b, B, b->trk, b->seprule, b->smap_on ? &b->smap : nullptr,
                                   b->smap_on ? b->srule : speed_rule_default(), r.pose, reset, nullptr, mode, nullptr,
-                                  nullptr, s), "separation launch");
+                                  nullptr, s, guarded ? &b->sguard : nullptr), "separation launch");
         if (rc) return rc;
+        // the protective hold: a held robot is parked in IDLE for the gate; the status launch brings its mode back
+        if (guarded) {
+            rc = hip_err(sep_hold(b, B, b->sguard, mode, reset, nullptr, mode, q ? q->remains : nullptr, s),
+                         "sep_hold launch");
+            if (rc) return rc;
+        }
     } else if (b->smap_on) {
         // speed zones: the stage limits of the robots that are about to solve, from the stage's pose (under strict an
         // invalid robot's mode is ERROR by now: its rows stay)
@@ -1381,7 +1502,8 @@ int nmpc_batch_node_cycle(nmpc_batch* b, int B, const nmpc_node_params* np, cons
     rc = node_tick(b, B, np, q, mode, r.pose, r.vel, steer, goal, segs, seg_stride, q ? nullptr : nseg, path_u, reset,
                    event, err, traj_out, n_solved, cmd, u0, status, qp_iter, qp_res, stream);
     if (rc) return rc;
-    return hip_err(launch_cycle_status(B, r.valid, in->strict ? 1 : 0, mode, event, q ? q->remains : nullptr, s),
+    return hip_err(launch_cycle_status(B, r.valid, in->strict ? 1 : 0, mode, event, q ? q->remains : nullptr,
+                                       guarded ? b->sep_held : nullptr, b->sep_mode_save, b->sep_remains_save, s),
                    "cycle_status launch");
 }
 
@@ -1569,6 +1691,67 @@ int nmpc_batch_stage_limits_from_tracks(nmpc_batch* b, int B, const nmpc_tracks*
         return tracks_write(b, B, *tracks, sep ? *sep : sep_rule_default(), map, rule ? *rule : speed_rule_default(),
                             pose, reset, mask, nullptr, vlim, gap, s);
     });
+}
+
+int nmpc_sep_guard_default(nmpc_sep_guard* g)
+{
+    if (!g) return set_err(NMPC_ERR_ARG, "separation guard is NULL");
+    *g = sep_guard_default();
+    return NMPC_OK;
+}
+
+int nmpc_batch_stage_limits_from_tracks_ex(nmpc_batch* b, int B, const nmpc_tracks* tracks, const nmpc_sep_rule* sep,
+                                           const nmpc_sep_guard* guard, const nmpc_speed_map* map,
+                                           const nmpc_speed_rule* rule, const float* pose, const unsigned char* reset,
+                                           const unsigned char* mask, float* vlim, float* gap, float* gap_all,
+                                           void* stream)
+{
+    const TraceRange trace("nmpc_batch_stage_limits_from_tracks_ex");
+    const char* bad = bad_tracks(tracks, sep, B);
+    if (!bad) bad = map ? bad_speed_map(map, rule) : bad_speed_rule(rule);
+    if (!bad && reset && !pose) bad = "tracks: reset needs pose";
+    if (!bad) bad = bad_guard(guard, sep ? sep->range : sep_rule_default().range, tracks->own_first);
+    if (!bad && gap_all && !guard) bad = "tracks: gap_all needs a guard";
+    if (!bad && guard && !pose) bad = "separation guard: pose is required (a held robot stands at it)";
+    return table_write(b, B, bad, sb_table, stream, "separation launch", [&](hipStream_t s) {
+        if (sep_scratch(b, tracks->M) || (guard && guard_scratch(b))) return hipErrorOutOfMemory;
+        return tracks_write(b, B, *tracks, sep ? *sep : sep_rule_default(), map, rule ? *rule : speed_rule_default(),
+                            pose, reset, mask, nullptr, vlim, gap, s, guard, gap_all);
+    });
+}
+
+int nmpc_batch_sep_hold(nmpc_batch* b, int B, const nmpc_sep_guard* guard, const unsigned char* mode,
+                        const unsigned char* reset, unsigned char* held_out, void* stream)
+{
+    const TraceRange trace("nmpc_batch_sep_hold");
+    if (B < 0) return set_err(NMPC_ERR_ARG, "B out of range [0, capacity]");
+    if (!guard) return set_err(NMPC_ERR_ARG, "separation guard is NULL");
+    if (const char* bad = bad_guard(guard, -1.0f, -2)) return set_err(NMPC_ERR_ARG, bad);
+    if (const int rc = check_batch(b, B)) return rc;
+    if (!b->sep_qa_ready)
+        return set_err(NMPC_ERR_ARG, "sep_hold: no nmpc_batch_stage_limits_from_tracks_ex call with a guard came before");
+    return hip_err(sep_hold(b, B, *guard, mode, reset, held_out, nullptr, nullptr, (hipStream_t)stream),
+                   "sep_hold launch");
+}
+
+int nmpc_batch_set_sep_guard(nmpc_batch* b, const nmpc_sep_guard* guard)
+{
+    if (const char* bad = bad_guard(guard, -1.0f, -2)) return set_err(NMPC_ERR_ARG, bad);
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (guard)
+        if (const int rc = guard_scratch(b)) return rc;
+    if (const int rc = guard_clear_held(b)) return rc;
+    b->sguard_on = guard != nullptr;
+    if (guard) b->sguard = *guard;
+    return NMPC_OK;
+}
+
+int nmpc_batch_sep_state(nmpc_batch* b, unsigned char** held)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (const int rc = guard_scratch(b)) return rc;
+    if (held) *held = b->sep_held;
+    return NMPC_OK;
 }
 
 int nmpc_batch_set_tracks(nmpc_batch* b, const nmpc_tracks* tracks, const nmpc_sep_rule* sep, int export_own)

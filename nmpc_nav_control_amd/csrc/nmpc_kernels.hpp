@@ -239,6 +239,7 @@ struct ExportTracksArgs {
     const float* pose;           // [3][B], or nullptr (then reset and mode are nullptr too)
     const unsigned char* reset;  // [B] or nullptr
     const unsigned char* mode;   // [B] or nullptr
+    const unsigned char* held;   // [cap] or nullptr: the protective hold's state; a held robot stands, like a reset one
     double* xy;
     int M, K, first;
 };
@@ -260,8 +261,37 @@ struct SepArgs {
     double cull2;               // a track whose box is farther than this (squared) from the robot's is skipped
     double* boxes;
     float* q;
+    // the guard form (nmpc_batch_stage_limits_from_tracks_ex with a guard; guard == 0: none of these is read). q is
+    // then qy, the minimum over the pairs that also have priority[j] >= the robot's own; qa [N+1][d.cap] takes the
+    // unfiltered minimum. A robot with held[i] != 0 stands at its pose and keeps the iterate's direction
+    int guard;
+    const int* priority;         // [M] or nullptr: no filter, qy == qa
+    const int* own_priority;     // [B] or nullptr: priority[own_first + i]
+    const unsigned char* held;   // [d.cap]
+    float* qa;
+    float* gap_all;              // [N+1][B] or nullptr: sqrtf(qa_k)
 };
 hipError_t launch_sep_min(const SepArgs& a, hipStream_t stream);
+// The protective hold (k_sep_hold): held' of every robot of [0, B) from the qa plane of the preceding writer call.
+// park, the cycle's: mode_rw is then the cycle's mode array; every robot's mode is saved to mode_save [cap] (and its
+// remains to remains_save when the queue's remains is given), and a robot with held' != 0 is parked in IDLE for the
+// gate. launch_cycle_status brings both back
+struct SepHoldArgs {
+    int B, N, cap;
+    const float* qa;             // [N+1][cap]
+    int last;                    // min(hold_stages, N)
+    float stop_gap, release_gap;
+    int hold;
+    const unsigned char* mode;   // [B] or nullptr: every robot is judged
+    const unsigned char* reset;  // [B] or nullptr
+    unsigned char* held;         // [cap]
+    unsigned char* held_out;     // [B] or nullptr
+    unsigned char* mode_rw;      // park: [B], else nullptr
+    unsigned char* mode_save;    // park: [cap]
+    const double* remains;       // park: [B] or nullptr
+    double* remains_save;        // park: [cap]
+};
+hipError_t launch_sep_hold(const SepHoldArgs& a, hipStream_t stream);
 // The frame table fr [2][cap] (fp64: every robot's origin x, then y) and the resident iterate's position rows.
 // frame_set: the masked robots of the first B take a new origin and the x and y row of every stage of xbar
 // ([(N+1)*nx][cap]) becomes (float)((double)x + (o_old - o_new)). The new origin is origin[2][B]; or, with pose_map
@@ -355,7 +385,10 @@ struct NodeInputArgs {
 hipError_t launch_node_input(const NodeInputArgs& a, hipStream_t stream);
 // the status rule of nmpc_batch_node_cycle after the tick, for the robots with valid[i] == 0: strict: event
 // INPUT_INVALID; else a mode that is still GOTO_POSE or FOLLOW_PATH becomes ERROR (remains, the queue's, NaN)
+// held [cap] or nullptr (the protective hold, before the rule above): a robot with held[i] != 0 was parked by
+// launch_sep_hold; it gets its mode back from mode_save, its remains from remains_save and the event HELD
 hipError_t launch_cycle_status(int B, const unsigned char* valid, int strict, unsigned char* mode, unsigned char* event,
-                               double* remains, hipStream_t stream);
+                               double* remains, const unsigned char* held, const unsigned char* mode_save,
+                               const double* remains_save, hipStream_t stream);
 
 }  // namespace nmpc

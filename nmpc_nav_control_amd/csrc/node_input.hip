@@ -214,10 +214,17 @@ __global__ void __launch_bounds__(kThreads) k_node_input(NodeInputArgs g)
 }
 
 __global__ void k_cycle_status(int B, const unsigned char* valid, int strict, unsigned char* mode, unsigned char* event,
-                               double* remains)
+                               double* remains, const unsigned char* held, const unsigned char* mode_save,
+                               const double* remains_save)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B || valid[i]) return;
+    if (i >= B) return;
+    if (held && held[i]) {  // the protective hold parked the robot in IDLE for the gate: the mode it had comes back
+        mode[i] = mode_save[i];
+        if (remains) remains[i] = remains_save[i];
+        if (event) event[i] = NMPC_NODE_EV_HELD;
+    }
+    if (valid[i]) return;
     if (strict) {
         if (event) event[i] = NMPC_NODE_EV_INPUT_INVALID;
     } else if (mode[i] == NMPC_NODE_GOTO_POSE || mode[i] == NMPC_NODE_FOLLOW_PATH) {
@@ -246,10 +253,12 @@ hipError_t launch_node_input(const NodeInputArgs& a, hipStream_t stream)
 }
 
 hipError_t launch_cycle_status(int B, const unsigned char* valid, int strict, unsigned char* mode, unsigned char* event,
-                               double* remains, hipStream_t stream)
+                               double* remains, const unsigned char* held, const unsigned char* mode_save,
+                               const double* remains_save, hipStream_t stream)
 {
     if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_cycle_status, grid_of(B), dim3(kThreads), 0, stream, B, valid, strict, mode, event, remains);
+    hipLaunchKernelGGL(k_cycle_status, grid_of(B), dim3(kThreads), 0, stream, B, valid, strict, mode, event, remains,
+                       held, mode_save, remains_save);
     return hipGetLastError();
 }
 

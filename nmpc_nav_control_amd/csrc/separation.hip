@@ -15,6 +15,13 @@
 // the boxes' squared distance is no larger; it is compared with range^2 (1 + 1e-5). Every comparison that involves a
 // NaN keeps the track. min is exact, so neither tiles nor chunks show in the bits; the file is compiled without
 // contraction (Makefile), so dx*dx + dy*dy is mul, mul, add.
+// The guard form (k_sep_min<true>, nmpc_sep_guard): a lane keeps two running minima per owned stage, qa over every
+// counting pair (the q of the form above) and qy over those whose track has priority[j] >= the robot's own; the
+// priority of a hit is one row-uniform load per hit, inside the loop bounded by 16. A held robot stands at its pose
+// like a reset one but keeps the iterate's direction. The cull's argument is unchanged: the filter only removes pairs
+// from the set the cull is conservative for, and qa is that set's minimum. k_sep_min<false> is the code above.
+// k_sep_hold: one lane per robot strides the stages 0..min(hold_stages, N) of the qa plane (instance-minor reads, a
+// trip count that no data decides) and applies the hysteresis of the protective hold.
 #include "nmpc_kernels.hpp"
 
 namespace nmpc {
@@ -31,6 +38,7 @@ __global__ void __launch_bounds__(kThreads) k_export_tracks(ExportTracksArgs a)
     if (e >= n) return;
     const int k = (int)(e / a.B), i = (int)(e % a.B);
     bool stand = a.reset && a.reset[i] != 0;
+    if (!stand && a.held) stand = a.held[i] != 0;
     if (!stand && a.mode) stand = !(a.mode[i] == NMPC_NODE_GOTO_POSE || a.mode[i] == NMPC_NODE_FOLLOW_PATH);
     const int kk = k <= a.N ? k : a.N;
     const float x = stand ? a.pose[i] : a.xbar[((size_t)kk * a.nx + 0) * a.cap + i];
@@ -68,6 +76,7 @@ __device__ inline double row_max(double v)
     return v;
 }
 
+template <bool Guard>
 __global__ void __launch_bounds__(kThreads) k_sep_min(SepArgs a)
 {
     const int row = threadIdx.x / kRow, lane = threadIdx.x % kRow;
@@ -77,17 +86,24 @@ __global__ void __launch_bounds__(kThreads) k_sep_min(SepArgs a)
     if (go && a.mask) go = a.mask[i] != 0;
     if (go && a.mode) go = a.mode[i] == NMPC_NODE_GOTO_POSE || a.mode[i] == NMPC_NODE_FOLLOW_PATH;
     const int ic = i < a.B ? i : 0;  // (a row without a robot reads robot 0's data, in bounds, and writes nothing)
-    const bool fresh = a.reset && a.reset[ic] != 0;
+    const bool fresh = a.reset && a.reset[ic] != 0;  // has no direction: h_k = 0
+    bool stand = fresh;                              // stands: the pose at every stage
+    int pown = 0;
+    if constexpr (Guard) {
+        stand = fresh || a.held[ic] != 0;
+        // (own_priority NULL: the host has checked own_first >= 0 and own_first + B <= M)
+        if (a.priority) pown = a.own_priority ? a.own_priority[ic] : a.priority[a.own_first + ic];
+    }
     const double ox = a.origin ? a.origin[ic] : 0.0, oy = a.origin ? a.origin[(size_t)cap + ic] : 0.0;
-    const float px = fresh ? a.pose[ic] : 0.0f, py = fresh ? a.pose[(size_t)a.B + ic] : 0.0f;
+    const float px = stand ? a.pose[ic] : 0.0f, py = stand ? a.pose[(size_t)a.B + ic] : 0.0f;
     const int own = a.own_first >= 0 ? a.own_first + i : -1;
     const int rsh = ((threadIdx.x % warpSize) / kRow) * kRow;  // the row's bits in the wave's ballot
 
     // the robot's horizon box in map coordinates
     double rlx = INFINITY, rhx = -INFINITY, rly = INFINITY, rhy = -INFINITY;
     for (int k = lane; k <= N; k += kRow) {
-        const float x = fresh ? px : a.xbar[((size_t)k * a.nx + 0) * cap + ic];
-        const float y = fresh ? py : a.xbar[((size_t)k * a.nx + 1) * cap + ic];
+        const float x = stand ? px : a.xbar[((size_t)k * a.nx + 0) * cap + ic];
+        const float y = stand ? py : a.xbar[((size_t)k * a.nx + 1) * cap + ic];
         const double X = (double)x + ox, Y = (double)y + oy;
         rlx = fmin(rlx, X); rhx = fmax(rhx, X);
         rly = fmin(rly, Y); rhy = fmax(rhy, Y);
@@ -98,18 +114,20 @@ __global__ void __launch_bounds__(kThreads) k_sep_min(SepArgs a)
     for (int k0 = 0; k0 <= N; k0 += kRow * kU) {
         double X[kU], Y[kU];
         float hx[kU], hy[kU], q[kU];
+        [[maybe_unused]] float qa[kU];
 #pragma unroll
         for (int u = 0; u < kU; u++) {
             const int k = k0 + lane + kRow * u;
             const int kc = k <= N ? k : N;  // (in bounds; a stage past N is not written)
             const int k1 = kc + 1 <= N ? kc + 1 : N, k2 = kc <= N - 1 ? kc : N - 1;
-            const float x = fresh ? px : a.xbar[((size_t)kc * a.nx + 0) * cap + ic];
-            const float y = fresh ? py : a.xbar[((size_t)kc * a.nx + 1) * cap + ic];
+            const float x = stand ? px : a.xbar[((size_t)kc * a.nx + 0) * cap + ic];
+            const float y = stand ? py : a.xbar[((size_t)kc * a.nx + 1) * cap + ic];
             X[u] = (double)x + ox;
             Y[u] = (double)y + oy;
             hx[u] = fresh ? 0.0f : a.xbar[((size_t)k1 * a.nx + 0) * cap + ic] - a.xbar[((size_t)k2 * a.nx + 0) * cap + ic];
             hy[u] = fresh ? 0.0f : a.xbar[((size_t)k1 * a.nx + 1) * cap + ic] - a.xbar[((size_t)k2 * a.nx + 1) * cap + ic];
             q[u] = INFINITY;
+            if constexpr (Guard) qa[u] = INFINITY;
         }
         for (int c = 0; c < M; c += kRow) {
             const int jt = c + lane;
@@ -123,6 +141,8 @@ __global__ void __launch_bounds__(kThreads) k_sep_min(SepArgs a)
             while (bits) {  // at most 16 rounds
                 const int j = c + __ffs(bits) - 1;
                 bits &= bits - 1;
+                [[maybe_unused]] bool yields = true;  // the robot gives way to this track: the pair enters qy
+                if constexpr (Guard) yields = !a.priority || a.priority[j] >= pown;
 #pragma unroll
                 for (int u = 0; u < kU; u++) {
                     const int k = k0 + lane + kRow * u;
@@ -133,7 +153,12 @@ __global__ void __launch_bounds__(kThreads) k_sep_min(SepArgs a)
                     const float qq = dx * dx + dy * dy;
                     bool counts = qq <= a.range2;  // (a NaN fails)
                     if (a.ahead_only) counts = counts && ((hx[u] == 0.0f && hy[u] == 0.0f) || dx * hx[u] + dy * hy[u] > 0.0f);
-                    if (counts) q[u] = fminf(q[u], qq);
+                    if constexpr (Guard) {
+                        if (counts) qa[u] = fminf(qa[u], qq);
+                        if (counts && yields) q[u] = fminf(q[u], qq);
+                    } else {
+                        if (counts) q[u] = fminf(q[u], qq);
+                    }
                 }
             }
         }
@@ -142,8 +167,36 @@ __global__ void __launch_bounds__(kThreads) k_sep_min(SepArgs a)
             for (int u = 0; u < kU; u++) {
                 const int k = k0 + lane + kRow * u;
                 if (k <= N) a.q[(size_t)k * cap + i] = q[u];
+                if constexpr (Guard)
+                    if (k <= N) {
+                        a.qa[(size_t)k * cap + i] = qa[u];
+                        if (a.gap_all) a.gap_all[(size_t)k * a.B + i] = sqrtf(qa[u]);
+                    }
             }
         }
+    }
+}
+
+// held' = reset ? 0 : (held ? m < release_gap : m < stop_gap), m the smallest gap over the protective field's stages
+// (fminf: a NaN never counts; +inf when nothing counts); a robot in a mode that does not solve, and every robot with
+// hold == 0, gets 0
+__global__ void __launch_bounds__(kThreads) k_sep_hold(SepHoldArgs a)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= a.B) return;
+    float m = INFINITY;
+    for (int k = 0; k <= a.last; k++) m = fminf(m, sqrtf(a.qa[(size_t)k * a.cap + i]));
+    const unsigned char md = a.mode ? a.mode[i] : (unsigned char)NMPC_NODE_GOTO_POSE;
+    const bool drives = md == NMPC_NODE_GOTO_POSE || md == NMPC_NODE_FOLLOW_PATH;
+    const bool fresh = a.reset && a.reset[i] != 0;
+    const bool was = a.held[i] != 0;
+    const bool now = a.hold && drives && !fresh && (was ? m < a.release_gap : m < a.stop_gap);
+    a.held[i] = now ? 1 : 0;
+    if (a.held_out) a.held_out[i] = now ? 1 : 0;
+    if (a.mode_rw) {  // the cycle: the gate sees a held robot in IDLE; k_cycle_status brings its mode back
+        a.mode_save[i] = md;
+        if (a.remains) a.remains_save[i] = a.remains[i];
+        if (now) a.mode_rw[i] = NMPC_NODE_IDLE;
     }
 }
 
@@ -168,7 +221,17 @@ hipError_t launch_sep_min(const SepArgs& a, hipStream_t stream)
         if (e != hipSuccess) return e;
     }
     const int R = kThreads / kRow;
-    hipLaunchKernelGGL(k_sep_min, dim3((a.B + R - 1) / R), dim3(kThreads), 0, stream, a);
+    if (a.guard)
+        hipLaunchKernelGGL(k_sep_min<true>, dim3((a.B + R - 1) / R), dim3(kThreads), 0, stream, a);
+    else
+        hipLaunchKernelGGL(k_sep_min<false>, dim3((a.B + R - 1) / R), dim3(kThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_sep_hold(const SepHoldArgs& a, hipStream_t stream)
+{
+    if (a.B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sep_hold, dim3((a.B + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -26,6 +26,8 @@ state; `rate` is robot ticks per second over the timed steps (solve + plant step
                 3 m range of every robot). The three variants have the frame table on with the same origins as their
                 `off`, so the tick is the same; `sep_us` is export + writer alone, timed back to back on the final
                 state, and `cull` what the box test kept, counted by tests/separation_ref.py on 256 of the robots
+                --guard: the writer's guard form (nmpc_batch_stage_limits_from_tracks_ex with seeded priorities
+                0..3) and nmpc_batch_sep_hold behind it; `guard.held` counts the robots the hold took at the end
 The writers are timed on 4096 robots with a mask on half of them: mean over 200 back-to-back launches."""
 import argparse
 import itertools
@@ -41,7 +43,7 @@ from nmpc_nav_control_amd.batch import BatchSolver, NodeParams  # noqa: E402
 from nmpc_nav_control_amd.fleet import Fleet  # noqa: E402
 from nmpc_nav_control_amd.scenario import DEFAULT_SEED, PARAMS  # noqa: E402
 from nmpc_nav_control_amd.path import PathQueue  # noqa: E402
-from nmpc_nav_control_amd.batch import Tracks  # noqa: E402
+from nmpc_nav_control_amd.batch import SepGuard, Tracks  # noqa: E402
 from tests import frame_cases  # noqa: E402  (the origins, stated once)
 from tests import separation_ref  # noqa: E402
 from tests.path_cases import random_paths  # noqa: E402
@@ -151,8 +153,10 @@ def timed(model, B, N, steps, warmup, label, fill, dev):
 SEP_PITCH = dict(off=10.0, spread=10.0, dense=1.33)
 
 
-def timed_separation(model, B, N, steps, warmup, label, dev):
-    """the closed loop with export + writer before every tick (label off: without them), every robot's origin on a grid"""
+def timed_separation(model, B, N, steps, warmup, label, dev, guard=False):
+    """the closed loop with export + writer before every tick (label off: without them), every robot's origin on a grid.
+    guard: the writer's guard form with seeded priorities, and the hold's launch behind it (the loop times the launches:
+    held is counted, the plain ticks do not act on it)"""
     f = Fleet(model, B, N, DEFAULT_SEED, dev)
     s = f.solver
     side = int(np.ceil(np.sqrt(B)))
@@ -161,10 +165,16 @@ def timed_separation(model, B, N, steps, warmup, label, dev):
     s.set_robot_frame(torch.from_numpy(origin).to(dev))
     xy = torch.zeros(N + 1, 2, B, dtype=torch.float64, device=dev)
     tr = Tracks(xy, own_first=0)
+    G = None
+    if guard:
+        pr = np.random.default_rng(DEFAULT_SEED).integers(0, 4, B).astype(np.int32)
+        G = SepGuard(torch.from_numpy(pr).to(dev))
 
     def sep():
         s.export_tracks(xy, first=0, pose=f.pose, reset=f.reset)
-        s.stage_limits_from_tracks(tr, pose=f.pose, reset=f.reset)
+        s.stage_limits_from_tracks(tr, pose=f.pose, reset=f.reset, guard=G)
+        if G is not None:
+            s.sep_hold(G, reset=f.reset, B=B)
 
     def tick():
         if label != "off":
@@ -189,6 +199,8 @@ def timed_separation(model, B, N, steps, warmup, label, dev):
         b.record()
         torch.cuda.synchronize()
         r["sep_us"] = round(a.elapsed_time(b) / 20 * 1e3, 1)
+        if G is not None:
+            r["guard"] = dict(held=int(s.sep_state().to_tensor()[0, :B].sum().item()))
         T = xy.cpu().numpy()
         pick = np.arange(0, B, max(1, B // 256))[:256]
         c = separation_ref.cull_counts_map(T[:, :, pick], T, own=pick)
@@ -280,6 +292,7 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=240)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--guard", action="store_true", help="separation: the guard form of the writer and the hold's launch")
     args = ap.parse_args()
     model, B, N = (x if x is not None else c for x, c in zip((args.model, args.batch, args.N), CONFIGS[args.config]))
     variants, writers = TABLES[args.table]
@@ -293,7 +306,8 @@ def main():
                     print(json.dumps(dict(r, repeat=rep)), flush=True)
                 continue
             if args.table == "separation":
-                print(json.dumps(dict(timed_separation(model, B, N, args.steps, args.warmup, label, dev), repeat=rep)),
+                print(json.dumps(dict(timed_separation(model, B, N, args.steps, args.warmup, label, dev,
+                                                       guard=args.guard and label != "off"), repeat=rep)),
                       flush=True)
                 continue
             r = timed(model, B, N, args.steps, args.warmup, label, fill, dev)
