@@ -970,6 +970,28 @@ typedef struct nmpc_launch_plan {
 int nmpc_batch_plan_ex(const nmpc_batch* b, int B, int mode, nmpc_launch_plan* plan);
 int nmpc_batch_plan(const nmpc_batch* b, int B, int* kernel, int* waves_per_robot, int* segments);
 
+/* The team kernel's hand-off iteration C of this handle: 0 = off, the create-time value; NMPC_HANDOFF_AUTO = the
+ * measured default, C = 16 (the best of 10, 12, 14, 16 on the metric launch, diff N = 40 with 4096 robots: +5.4 %
+ * same-box); the environment variable NMPC_AMD_HANDOFF overrides the create-time value (A/B runs). It is off at
+ * create because a handed-over robot's result is the segmented kernel's, equal to the plain kernel's only within
+ * the bars below: whoever owns several handles of one fleet (other layouts, stream groups) sets all of them alike, as
+ * nmpc_nav_control_amd/fleet.py does for a diff fleet alone on the device. A team-kernel launch that qualifies runs k_sqp_rti_team_ho: a robot whose IPM has
+ * not stopped at the top of iteration C leaves the four-robots-per-wave loop there, and one wave of its block finishes
+ * it alone in the segmented form, four horizon segments on the wave's four rows, inside the same launch. The rule
+ * looks at the robot's own iteration count only. The iteration count, the warm rule and the stopping rule count both
+ * parts as one solve; a robot that was handed over ends with the segmented kernel's arithmetic (status equal, IPM
+ * count within a few iterations, u0 within the fp32 bars of the row-parallel kernel). A launch qualifies with the
+ * single-direction IPM, in solve and run mode (not run_path), unsplit and with at most one wave per SIMD, N a multiple
+ * of 4 with N >= 8, diff or tric, diff's wide records, every per-robot table off and the block's LDS (four resume
+ * slices) within the device's; every other launch keeps the plain kernel. C >= qp_iter_max hands nobody over.
+ * nmpc_batch_plan_handoff reports the decision for a launch of B robots (mode: NMPC_PLAN_*): iteration = C or 0,
+ * segments = the resumed form's horizon segments or 0, lds_bytes = the block's LDS or 0. Each output may be NULL.
+ * nmpc_batch_plan_ex describes the same launch as the team kernel (kernel 0); its record_layout and warm_tag are the
+ * hand-off launch's (wide). */
+#define NMPC_HANDOFF_AUTO (-1)
+int nmpc_batch_set_handoff(nmpc_batch* b, int iteration);
+int nmpc_batch_plan_handoff(const nmpc_batch* b, int B, int mode, int* iteration, int* segments, size_t* lds_bytes);
+
 /* Bench / test harness: closed-loop plant step and path-reference regeneration for B robots
  * (see DESIGN.md "Synthetic closed loop"). All device pointers, [field][B]:
  *   path [6][B] = {x0, y0, th0, kappa, speed, length} circular-arc paths; goal-pose robots have length < 0

@@ -155,7 +155,7 @@ BATCH_SYMBOLS = [
     "nmpc_model_dims", "nmpc_model_params_default", "nmpc_model_params_set_limits", "nmpc_batch_create",
     "nmpc_batch_destroy", "nmpc_batch_set_params", "nmpc_batch_get_params", "nmpc_batch_init_iterate",
     "nmpc_batch_solve", "nmpc_batch_solve_iterate", "nmpc_batch_run", "nmpc_batch_run_path", "nmpc_batch_follow_path", "nmpc_batch_node_tick", "nmpc_node_params_default",
-    "nmpc_batch_node_tick_queue", "nmpc_path_queue_default", "nmpc_batch_state", "nmpc_batch_warm_state", "nmpc_batch_warm_rule", "nmpc_batch_plan", "nmpc_batch_plan_ex", "nmpc_batch_set_record_layout", "nmpc_batch_forget_warm", "nmpc_batch_set_kernel", "nmpc_batch_set_schedule",
+    "nmpc_batch_node_tick_queue", "nmpc_path_queue_default", "nmpc_batch_state", "nmpc_batch_warm_state", "nmpc_batch_warm_rule", "nmpc_batch_plan", "nmpc_batch_plan_ex", "nmpc_batch_set_handoff", "nmpc_batch_plan_handoff", "nmpc_batch_set_record_layout", "nmpc_batch_forget_warm", "nmpc_batch_set_kernel", "nmpc_batch_set_schedule",
     "nmpc_batch_set_robot_params", "nmpc_batch_set_robot_limits", "nmpc_batch_robot_params",
     "nmpc_batch_clear_robot_params",
     "nmpc_batch_set_stage_bounds", "nmpc_batch_set_stage_limits", "nmpc_batch_shift_stage_bounds",
@@ -246,6 +246,8 @@ def lib():
     L.nmpc_batch_warm_rule.argtypes = [vp, c_int_p, c_int_p, c_int_p]
     L.nmpc_batch_plan.argtypes = [vp, ctypes.c_int, c_int_p, c_int_p, c_int_p]
     L.nmpc_batch_plan_ex.argtypes = [vp, i, i, ctypes.POINTER(LaunchPlan)]
+    L.nmpc_batch_set_handoff.argtypes = [vp, i]
+    L.nmpc_batch_plan_handoff.argtypes = [vp, i, i, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_size_t)]
     L.nmpc_batch_set_record_layout.argtypes = [vp, i]
     L.nmpc_batch_set_robot_params.argtypes = [vp, i, ctypes.POINTER(RobotParamsStruct), vp, vp]
     L.nmpc_batch_set_robot_limits.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]

@@ -219,6 +219,21 @@ class BatchSolver:
                     record_layout="split" if p.record_layout else "wide", warm_tag=p.warm_tag,
                     record_bytes=p.record_bytes)
 
+    def set_handoff(self, iteration):
+        """The team kernel's hand-off iteration C of this handle (nmpc_batch_set_handoff; 0: off, the create-time setting;
+        -1: the measured default, NMPC_HANDOFF_AUTO): in the launches
+        that qualify, a robot whose IPM has not stopped at the top of iteration C is finished alone by one wave of its
+        block, in the segmented form."""
+        check(lib().nmpc_batch_set_handoff(self._h, int(iteration)), "nmpc_batch_set_handoff")
+
+    def plan_handoff(self, B, mode="solve"):
+        """Whether a launch of B robots takes the hand-off (nmpc_batch_plan_handoff): dict with iteration (C, or 0:
+        the plain kernel), segments and lds_bytes of the hand-off form. mode: 'solve', 'run' or 'run_path'."""
+        it, sg, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+        check(lib().nmpc_batch_plan_handoff(self._h, int(B), PLAN_MODES[mode], ctypes.byref(it), ctypes.byref(sg),
+                                            ctypes.byref(lds)), "nmpc_batch_plan_handoff")
+        return dict(iteration=it.value, segments=sg.value, lds_bytes=lds.value)
+
     def set_kernel(self, kernel):
         """'team' (16-lane team per robot): the only kernel."""
         check(lib().nmpc_batch_set_kernel(self._h, KERNELS[kernel]), "nmpc_batch_set_kernel")

@@ -62,6 +62,13 @@ struct nmpc_batch {
     // the team kernel's single-direction record layout (NMPC_REC_WIDE / NMPC_REC_SPLIT), fixed per handle: resolved
     // at create time from this handle alone and changed only by nmpc_batch_set_record_layout
     int rec_split = 0;
+    // the team kernel's hand-off iteration C (nmpc_batch_set_handoff; NMPC_AMD_HANDOFF overrides at create, A/B runs):
+    // launches that qualify (plan_launch) run k_sqp_rti_team_ho, whose teams leave the team loop unfinished at the top
+    // of IPM iteration C and are finished one robot per wave in the segmented form. 0: off, the create-time
+    // value: a handed-over robot ends with the segmented kernel's arithmetic, and the handles of one fleet in different
+    // layouts or groupings are held to each other bit for bit, so the owner of the fleet turns it on, for all of them
+    // (fleet.py, as for the record layout). NMPC_HANDOFF_AUTO: the measured default kHandoffDefault
+    int handoff = 0;
     double* path_err = nullptr;  // [2][capacity] path errors of nmpc_batch_follow_path when the caller keeps none
                                  // (allocated at the first such call)
     // node ticks (nmpc_batch_node_tick), allocated at the first one: the gate's reference poses [N+1][3][capacity]
@@ -200,6 +207,7 @@ hipError_t launch_m(nmpc_batch* b, const KArgs& a, int mode, hipStream_t s)
 {
     if (a.rowpar) return launch_sqp_rti_rowpar<M>(b->kp, a, mode, s);
     if (a.stage_in_n > 0 || a.stage_out_n > 0) return hipErrorInvalidValue;  // (only the row-parallel kernel stages)
+    if (a.handoff > 0) return launch_sqp_rti_team_ho<M>(b->kp, a, mode, s);
     return launch_sqp_rti_team<M>(b->kp, a, mode, s);
 }
 
@@ -294,7 +302,34 @@ int warm_tag_of(const nmpc_batch* b, int rec_split)
 // flags. schedule() launches from it and nmpc_batch_plan_ex reports it; nothing else decides any of the four
 struct LaunchPlan {
     int waves, seg, rec_split, warm_tag;
+    int handoff;     // > 0: k_sqp_rti_team_ho with this hand-off iteration (then seg = kHandoffSeg, rec_split = 0)
+    size_t ho_lds;   // its LDS bytes per block
 };
+
+// Whether a team-kernel launch of B robots takes the in-block hand-off (sqp_rti_team_ho.hip), and its LDS per block.
+// The form exists for the single-direction rule, solve and run mode (the march of run_path owns the LDS), unsplit
+// launches with at most one wave per SIMD (then one block per CU: the four resume slices have the CU's LDS to
+// themselves), horizons of four segments of at least two stages, models whose segmented tick fits one wave per SIMD
+// (diff, tric), diff's wide records (tric's hand-off launches take them too) and with every per-robot table off; a
+// cap at or above qp_iter_max hands nobody off. Everything else keeps the plain kernel
+inline int handoff_of(const nmpc_batch* b, int B)
+{
+    (void)B;  // (the rule looks at no batch size: a fleet split into stream groups hands over the same robots)
+    return b->handoff == NMPC_HANDOFF_AUTO ? kHandoffDefault : b->handoff;
+}
+
+template <class M>
+size_t handoff_ok(const nmpc_batch* b, int B, bool path_march)
+{
+    if (handoff_of(b, B) <= 0 || b->kp.ipm != NMPC_IPM_SINGLE || path_march) return 0;
+    if ((B + 3) / 4 > b->n_simd || B <= b->split_max) return 0;  // dense, split (schedule())
+    if (b->rparams.on || b->sbounds.on || b->rmodel.on) return 0;
+    if (b->prm.model == NMPC_MODEL_DIFF2AMR && b->rec_split) return 0;
+    const size_t lds = team_ho_lds_bytes<M>(b->prm.N);
+    const int blocks = (B + 15) / 16, n_cu = b->n_cu > 0 ? b->n_cu : 1;
+    if (lds == 0 || lds > b->lds_per_cu / (size_t)((blocks + n_cu - 1) / n_cu)) return 0;
+    return lds;
+}
 
 LaunchPlan plan_launch(const nmpc_batch* b, int B, bool path_march, int mode)
 {
@@ -306,6 +341,14 @@ LaunchPlan plan_launch(const nmpc_batch* b, int B, bool path_march, int mode)
     }
     // the row-parallel kernel keeps the wide single-direction records; the team kernel the handle's layout
     p.rec_split = (!p.waves && b->kp.ipm == NMPC_IPM_SINGLE) ? b->rec_split : 0;
+    if (!p.waves) {
+        p.ho_lds = with_model(b->prm.model, [&](auto m) { return handoff_ok<decltype(m)>(b, B, path_march); });
+        if (p.ho_lds) {
+            p.handoff = handoff_of(b, B);
+            p.seg = kHandoffSeg;
+            p.rec_split = 0;
+        }
+    }
     p.warm_tag = warm_tag_of(b, p.rec_split);
     return p;
 }
@@ -322,6 +365,7 @@ hipError_t schedule(nmpc_batch* b, KArgs& a, int mode, hipStream_t s)
     a.seg = p.seg;
     a.rec_split = p.rec_split;
     a.warm_tag = p.warm_tag;
+    a.handoff = p.handoff;
     if (a.rowpar && !a.n_active) return hipSuccess;  // one robot per wave: nothing to place
     a.dense = ((a.B + 3) / 4 > b->n_simd) ? 1 : 0;  // 4 teams per wave
     // small batches leave most of the chip idle: one wave per robot, whose spare rows integrate P0's stages
@@ -928,6 +972,7 @@ int nmpc_batch_create(const nmpc_model_params* prm, int capacity, nmpc_batch** o
     if (const char* v = std::getenv("NMPC_AMD_SEG")) b->seg = std::atoi(v);  // A/B: 0 = serial, S = S segments
     if (const char* v = std::getenv("NMPC_AMD_ROWPAR_W")) b->rowpar_w = std::atoi(v) == 1 ? 1 : 2;  // A/B
     if (const char* v = std::getenv("NMPC_AMD_SEG_ROWS")) b->seg_rows = std::atoi(v) == 8 ? 8 : 4;  // A/B
+    if (const char* v = std::getenv("NMPC_AMD_HANDOFF")) b->handoff = std::atoi(v) > 0 ? std::atoi(v) : 0;  // A/B: 0 = off
     const int N = prm->N;
     const size_t S = (size_t)capacity;
     hipError_t e;
@@ -1874,10 +1919,32 @@ int nmpc_batch_plan_ex(const nmpc_batch* b, int B, int mode, nmpc_launch_plan* p
     const LaunchPlan p = plan_launch(b, B, mode == NMPC_PLAN_RUN_PATH, mode == NMPC_PLAN_SOLVE ? kModeSolve : kModeRun);
     plan->kernel = p.waves ? 1 : 0;
     plan->waves_per_robot = p.waves;
-    plan->segments = p.seg;
+    plan->segments = p.waves ? p.seg : 0;  // (the team kernel reports none, with or without the hand-off)
     plan->record_layout = p.rec_split ? NMPC_REC_SPLIT : NMPC_REC_WIDE;
     plan->warm_tag = p.warm_tag;
     plan->record_bytes = rec_footprint(b);
+    return NMPC_OK;
+}
+
+int nmpc_batch_set_handoff(nmpc_batch* b, int iteration)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (iteration < 0 && iteration != NMPC_HANDOFF_AUTO)
+        return set_err(NMPC_ERR_ARG, "the hand-off iteration must be >= 0 (0: off) or NMPC_HANDOFF_AUTO");
+    b->handoff = iteration;
+    return NMPC_OK;
+}
+
+int nmpc_batch_plan_handoff(const nmpc_batch* b, int B, int mode, int* iteration, int* segments, size_t* lds_bytes)
+{
+    if (!b) return set_err(NMPC_ERR_ARG, "batch is NULL");
+    if (B < 0 || B > b->capacity) return set_err(NMPC_ERR_ARG, "B out of range");
+    if (mode != NMPC_PLAN_SOLVE && mode != NMPC_PLAN_RUN && mode != NMPC_PLAN_RUN_PATH)
+        return set_err(NMPC_ERR_ARG, "mode must be NMPC_PLAN_SOLVE, NMPC_PLAN_RUN or NMPC_PLAN_RUN_PATH");
+    const LaunchPlan p = plan_launch(b, B, mode == NMPC_PLAN_RUN_PATH, mode == NMPC_PLAN_SOLVE ? kModeSolve : kModeRun);
+    if (iteration) *iteration = p.handoff;
+    if (segments) *segments = p.handoff ? p.seg : 0;
+    if (lds_bytes) *lds_bytes = p.handoff ? p.ho_lds : 0;
     return NMPC_OK;
 }
 

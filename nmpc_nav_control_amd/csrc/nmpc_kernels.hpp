@@ -110,6 +110,10 @@ struct KArgs {
     // per-robot model parameters (robot_tables.hip): the handle's model table [NP][sstride]; nullptr: the table is off
     // and every robot takes KParams::p. While it is on, KParams::p reaches no launch (robot_vals, sqp_steps.hpp)
     const float* rmodel;
+    // k_sqp_rti_team_ho (sqp_rti_team_ho.hip): the hand-off iteration C > 0; a team that has not stopped at the top of
+    // IPM iteration C leaves the team loop, and a wave of its block finishes the robot in the segmented one-wave form
+    // with `seg` segments. 0: every other launch. (The last field: the arguments before it keep their offsets.)
+    int handoff;
 };
 
 // Rows of the per-robot table, in this order: lbx[NBX] ubx[NBX] lbu[NBU] ubu[NBU] W[NY] W_e[NX]
@@ -159,6 +163,18 @@ template <class M>
 hipError_t launch_sqp_rti_rowpar(const KParams& P, const KArgs& a, int mode, hipStream_t stream);
 template <class M>
 size_t rowpar_lds_bytes(int N, int mode, int seg);
+// the team kernel with the in-block hand-off (sqp_rti_team_ho.hip; a.handoff > 0, a.seg = kHandoffSeg): diff and tric,
+// solve and run mode, unsplit launches with at most one wave per SIMD, wide records, every per-robot table off.
+// team_ho_lds_bytes: the LDS of one block (the hand-off list and four resume slices), 0 for a model or horizon it
+// does not serve
+constexpr int kHandoffSeg = 4;  // one segment per DPP row of the resuming wave
+// the hand-off iteration of NMPC_HANDOFF_AUTO (nmpc_batch_set_handoff; a handle is created with 0, off): the best of {10, 12, 14, 16} on the
+// metric config, diff N = 40 B = 4096, +5.4 % same-box (profiles/r10/ab/handoff.txt); 0 = off
+constexpr int kHandoffDefault = 16;
+template <class M>
+hipError_t launch_sqp_rti_team_ho(const KParams& P, const KArgs& a, int mode, hipStream_t stream);
+template <class M>
+size_t team_ho_lds_bytes(int N);
 constexpr int kSegMax = 16;  // most horizon segments of the segmented row-parallel kernel
 // rmodel: the handle's model table when it is on (the plant then steps each robot with its own column), else nullptr
 template <class M>

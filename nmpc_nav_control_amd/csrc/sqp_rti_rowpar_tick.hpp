@@ -1,17 +1,44 @@
 // sqp_rti_rowpar_tick.hpp -- the text of one row-parallel SQP-RTI tick: the body of k_sqp_rti_rowpar and of
-// k_sqp_rti_rowtab (sqp_rti_rowpar.hip), which include it inside their braces with M, W, SEG, MT, P, a and mode in
-// scope. Not a header in its own right: no include guard, nothing at namespace scope.
+// k_sqp_rti_rowtab (sqp_rti_rowpar.hip), which include it inside their braces with M, W, SEG, MT, RESUME, rs, P, a and
+// mode in scope. Not a header in its own right: no include guard, nothing at namespace scope.
+//
+// RESUME (k_sqp_rti_team_ho, sqp_rti_team_ho.hip: W = 1, SEG): the tick of a robot whose team left the team loop
+// unfinished, run by one wave of the team's block. It starts at the top of IPM iteration rs.it with the scalars in rs
+// (TickResume, rowpar_layout.hpp): no staging, no reset, no P0 -- the records, multipliers and DZ plane are where the
+// team kernel left them --, the wave's LDS slice rs.lds (ResumeLds) in place of the block's, and the direction of
+// iteration rs.it - 1 copied from the DZ plane into the slice. Everything from phase A on is the text below, unchanged.
+//
+// One wave per robot (W = 1): the phase boundaries are a wave-local fence, not the block barrier (blk_sync). In a
+// one-wave block the two order the same accesses, and the waves of a hand-off block, each with a robot of its own
+// and an iteration count of its own, could not share a block barrier. The fence is the barrier's own (workgroup scope:
+// LDS and global memory), not lds_fence() alone: phase A's record stores are read by other lanes of the wave in phase C.
     using R = RowRec<M>;
     constexpr int NX = M::NX, NU = M::NU, NV = R::NV, NGV = R::NGV, RS = R::RS, RSS = R::RSS;
     constexpr bool QM = rec_quad_major<NV>();
     constexpr int ROWS = 4 * W;
+    static_assert(!RESUME || (W == 1 && SEG && !MT), "the resumed tick: one wave, segmented, no model table");
     // node ticks: block s takes the robot of slot s of the order, for the first *n_active slots (the robots that
     // solve); plain launches (order == nullptr): block i = robot i
-    if ((int)blockIdx.x >= a.B || (a.n_active && (int)blockIdx.x >= *a.n_active)) return;
-    const int inst = a.order ? __builtin_amdgcn_readfirstlane(a.order[blockIdx.x]) : (int)blockIdx.x;
-    if (inst >= a.B) return;
-    const int tid = (int)threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (an SGPR: branches on it are wave-uniform)
+    if constexpr (!RESUME) {
+        if ((int)blockIdx.x >= a.B || (a.n_active && (int)blockIdx.x >= *a.n_active)) return;
+    }
+    const int inst = RESUME ? rs.inst : (a.order ? __builtin_amdgcn_readfirstlane(a.order[blockIdx.x]) : (int)blockIdx.x);
+    if constexpr (!RESUME) {
+        if (inst >= a.B) return;
+    }
+    const int tid = RESUME ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+    const int wave = RESUME ? 0 : __builtin_amdgcn_readfirstlane(tid >> 6);  // (an SGPR: branches on it are wave-uniform)
+    // (W1Barrier, rowpar_layout.hpp: the checker build lib/chk_w1bar keeps the block barrier in the one-wave kernels,
+    // as before the hand-off; never in a resumed tick, whose block has other waves)
+    constexpr bool kW1Fence = RESUME || !W1Barrier<>::value;
+    auto blk_sync = [&]() {
+        if constexpr (W == 1 && kW1Fence) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            lds_fence();
+        } else {
+            __syncthreads();
+        }
+    };
     const int q = tid >> 4;  // row of the block: stage-parallel phases take stages q, q + ROWS, ...
     const int r = tid & 15;  // slot: variable r of the stage (as a team lane)
     const bool wr = tid < 16;  // the lanes that store the serial phases' results
@@ -45,7 +72,7 @@
 
     // ---- staged capsule input (one robot): host-mapped block -> device block, every thread's loads in flight
     // together (one round trip of host memory instead of a copy launch and its dispatch gap before this kernel)
-    if (a.stage_in_n > 0) {
+    if (!RESUME && a.stage_in_n > 0) {
         constexpr int T = 64 * W, U = 8;
         for (int e0 = 0; e0 < a.stage_in_n; e0 += T * U) {
             float v[U];
@@ -65,7 +92,7 @@
     }
 
     // ---- reset ({name}_acados_reset: zero iterate) ----------------------------------------------------------
-    if (a.reset && a.reset[inst]) {
+    if (!RESUME && a.reset && a.reset[inst]) {
         for (int e = tid; e < (N + 1) * NX; e += 64 * W) XB(e / NX, e % NX) = 0.0f;
         for (int e = tid; e < N * NU; e += 64 * W) UBAR(e / NU, e % NU) = 0.0f;
         __syncthreads();
@@ -75,13 +102,14 @@
     float x0[NX];
     const X0Lane xl = load_x0<M>(P, a, mode, inst, lc, mp, x0);
     const float pose_th = xl.pose_th, x0_lane = xl.x0_lane;
-    float we_lane = xl.we_lane;  // (run mode: + the terminal hack, before P0c)
+    float we_lane = RESUME ? rs.we_lane : xl.we_lane;  // (run mode: + the terminal hack, before P0c)
 
     // ---- P0a: RK4 linearisation of stage k on row k mod 4 -> LDS [k][field][lane] -----------------------------
     // (StageLds, sqp_steps.hpp); run mode also the stage's reference pose in my_traj
     using SL = StageLds<M>;
     constexpr int SF = SL::SF;
-    extern __shared__ float s_row[];
+    extern __shared__ float s_blk[];
+    float* const s_row = RESUME ? rs.lds : s_blk;  // (RESUME: the wave's slice; only lpad, ItLds and SegLayout live there)
     float* const s_stg = s_row;
     float* const my_traj = s_row + (size_t)(N + 1) * SF * 16;
     float* const s_red = my_traj + (size_t)(N + 1) * 3;  // [W][8] per-wave partial reductions
@@ -90,7 +118,7 @@
     // wave holds identical values and takes identical decisions; the barrier is also the phase boundary
     auto block_combine = [&](float (&v)[6], const int (&op)[6], int n) {
         if constexpr (W == 1) {
-            __syncthreads();
+            blk_sync();
         } else {
             if ((tid & 63) == 0)
                 for (int i = 0; i < n; i++) s_red[wave * 8 + i] = v[i];
@@ -109,11 +137,11 @@
     const int len = (mode == kModeRun) ? (a.traj_len ? a.traj_len[inst] : N + 1) : 0;
     // a per-lane LDS slot nobody reads: the target of P0's stores for lanes / rounds without data (a store under a
     // lane mask leaves the compiler's later waits uncounted, i.e. full drains)
-    float* const lpad = s_row + RowLds<M>::pad_off(N) + (tid & 63);
+    float* const lpad = s_row + (RESUME ? 0 : RowLds<M>::pad_off(N)) + (tid & 63);
     // the IPM's per-iteration stage fields (ItLds): reads of idle lanes take slot 0, writes of lanes without an entry
     // go to their pad
     using IT = ItLds<M>;
-    float* const it_lds = s_row + RowLds<M>::it_off(N);
+    float* const it_lds = s_row + (RESUME ? ResumeLds<M>::it_off() : RowLds<M>::it_off(N));
     const int rv = lv ? r : 0;
     auto it_rd = [&](int k, int f) -> float { return it_lds[((size_t)k * IT::NF + f) * NV + rv]; };
     auto it_wr = [&](int k, int f, bool w) -> float* { return w ? it_lds + ((size_t)k * IT::NF + f) * NV + r : lpad; };
@@ -161,7 +189,7 @@
             }
         }
     };
-    if (!kP0Ov || !w0) {
+    if (!RESUME && (!kP0Ov || !w0)) {
         struct In {
             float x[NX], u[NU], y, xnext, tq;
             float2 l;
@@ -239,7 +267,7 @@
         for (int j = 0; j < NU; j++) ub0[j] = UBAR(0, j);
         const_rows<M>(P, mp, lc, r, xb0, ub0, gcol, grow);
     }
-    if constexpr (!kP0Ov) __syncthreads();  // the stage inputs of every row are in LDS
+    if constexpr (!kP0Ov && !RESUME) blk_sync();  // the stage inputs of every row are in LDS
     RP_STAMP(1);
 
     // ---- P0b (serial): the dynamics-feasible initial iterate dx_{k+1} = A_k dx_k + b_k on wave 0 and, in run mode,
@@ -249,7 +277,7 @@
     // scalar branches per stage, 575 cycles per stage step at one robot; profiles/r06/ab/p0b_w4.txt)
     float* const s_dx = s_red + 32;                  // [N+1][16]
     float* const s_ref = s_dx + (size_t)(N + 1) * 16;  // [N+1][3]
-    if (w0) {
+    if (!RESUME && w0) {
         struct Stg {
             float b, g[NGV];
         };
@@ -294,7 +322,7 @@
         }
         s_dx[N * 16 + r] = dx;
     }
-    if (mode == kModeRun && wave == W - 1) {
+    if (!RESUME && mode == kModeRun && wave == W - 1) {
         // (rows of the wave compute the same values; lanes 0-2 of each row store them, the rest store to a pad)
         wait_stage(N);  // (overlap: every round's reference poses)
         RefUnwrap ref(pose_th);
@@ -325,11 +353,12 @@
             if (k + 2 == N) break;
         }
     }
-    __syncthreads();
+    if (!RESUME) blk_sync();
     RP_STAMP(2);
 
     // ---- P0c (stage-parallel): gradient, bounds, slacks, multipliers and the record of stage k on row k mod ROWS
-    if (mode == kModeRun && P.terminal_hack)
+    // (RESUME: the team form's P0 wrote the records, and rs.we_lane is the terminal weight after the hack)
+    if (!RESUME && mode == kModeRun && P.terminal_hack)
         we_lane = terminal_weight(lc, we_lane, s_ref[N * 3] == s_ref[(N - 1) * 3] && s_ref[N * 3 + 1] == s_ref[(N - 1) * 3 + 1] &&
                                                    s_ref[N * 3 + 2] == s_ref[(N - 1) * 3 + 2]);
     // (the robot's own largest stage weight when the per-robot table is on)
@@ -340,7 +369,7 @@
     const bool sb_on = a.sbounds != nullptr;
     StageBox sbx{};
     if (sb_on) sbx = stage_box_ctx<M>(a, inst, lc, r);
-    for (int j = 0; j < NR; j++) {
+    for (int j = 0; !RESUME && j < NR; j++) {
         const int kr = j * ROWS + q;
         const bool kv = kr <= N;
         const int k = kv ? kr : N;
@@ -374,7 +403,7 @@
         for (int i = 0; i < NGV; i++) rec[R::GV + i] = (k < N && lv) ? st[SL::gv(i)] : 0.0f;
         rec_store_range<0, RSS, RS, QM>(kv ? tbase_own + (size_t)k * KS : tdummy, rec);  // idle slots: own unused slot
     }
-    {
+    if (!RESUME) {
         float v[6] = {wave_sum_rows(row_sum16(lv ? sum_c0 : 0.0f)), 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         const int op[6] = {0, 0, 0, 0, 0, 0};
         block_combine(v, op, 1);
@@ -454,7 +483,7 @@
     // SEG: the segment area of the LDS (RowLds / SegLayout), and the serial adjoint pass of the stopping rule:
     // pi_k = c0_x + A_k' pi_{k+1} on the state slots, the input stationarity residual c0_u + B_k' pi_{k+1}
     const SegLayout<M> SegL(SEG ? a.seg : 1);
-    float* const seg_lds = s_row + (SEG ? RowLds<M>::seg_off(N, a.seg) : 0);
+    float* const seg_lds = s_row + (RESUME ? ResumeLds<M>::seg_off(N) : (SEG ? RowLds<M>::seg_off(N, a.seg) : 0));
     auto adjoint = [&](float& res_stat, float& cpi_max) {
         float piv = 0.0f, rs = 0.0f, cm = 0.0f;
         serial(N, 0, -1, ld_adj, [&](int k, float (&rc)[RS]) {
@@ -475,10 +504,17 @@
     // ---- interior-point iterations (single-direction rule) -----------------------------------------------------
     int status = 0, it_done = 0;
     float exit_res[3] = {0.0f, 0.0f, 0.0f};
-    float alpha = 0.0f, sigma_mu = 0.0f, mu_prev = 3.0e38f;
-    float tg_rhs = P.sd_hi * sum_c0 * inv_m2;
+    float alpha = RESUME ? rs.alpha : 0.0f, sigma_mu = RESUME ? rs.sigma_mu : 0.0f, mu_prev = RESUME ? rs.mu_prev : 3.0e38f;
+    float tg_rhs = RESUME ? rs.tg_rhs : P.sd_hi * sum_c0 * inv_m2;
     int bseg_runs = 0;  // (SEG) executions of phase B so far
-    for (int it = 0;; it++) {
+    if constexpr (RESUME) {
+        // the direction the team form's last forward sweep left in the DZ plane ([robot][stage][16], behind the
+        // records), into the slice: phase A of iteration rs.it applies it (lanes without an entry hold P0's zero)
+        const float* const dzp = a.scratch + (size_t)a.sstride * (N + 1) * KS + (size_t)inst * (N + 1) * 16 + rv;
+        for (int k = q; k <= N; k += ROWS) *it_wr(k, IT::DZ, lv) = dzp[(size_t)k * 16];
+        blk_sync();
+    }
+    for (int it = RESUME ? rs.it : 0;; it++) {
         // phase A (stage-parallel): apply the previous step, residuals, barrier weight, rhs terms
         const float a_upd = (it > 0) ? alpha : 0.0f;
         float res_ineq = 0.0f, sum_c = 0.0f, max_c = 0.0f, lam_max = 0.0f, sc0 = 1.0f, nanf_ = 0.0f;
@@ -1000,7 +1036,7 @@
                 }
                 RP_MSTAMP(5, 0);
             }
-            __syncthreads();  // the boundary states and costates
+            blk_sync();  // the boundary states and costates
             RP_MSTAMP(7, 0);
             RP_STAMP(5 + 4 * it);
             // The master's factorisations work in fp64 on the segments' value matrices, whose entries carry the barrier
@@ -1146,7 +1182,7 @@
                     if (j + 1 == Ls) break;
                 }
             }
-            __syncthreads();  // the directions of every stage
+            blk_sync();  // the directions of every stage
         } else {
             // phase B (serial, N -> 0): adjoint, fp64 classic Riccati step, rhs / forward substitution
             double Lrow[NV];
@@ -1253,7 +1289,7 @@
                 it_done = it;
                 break;
             }
-            __syncthreads();  // LR / LM of every stage
+            blk_sync();  // LR / LM of every stage
 
             // phase C (serial, 0 -> N): the direction's input part from the stored factor, its state part from the
             // dynamics; every row the same (identical DZ stores)
@@ -1295,7 +1331,7 @@
                     if (k < N) dxs = dyn(rc, dz);
                 });
             }
-            __syncthreads();  // the directions of every stage
+            blk_sync();  // the directions of every stage
             RP_STAMP(5 + 4 * it);
         }
 
@@ -1382,7 +1418,7 @@
         }
     }
     // ---- staged capsule output: device block -> host-mapped block once every output above is stored
-    if (a.stage_out_n > 0) {
+    if (!RESUME && a.stage_out_n > 0) {
         __threadfence_block();
         __syncthreads();
         for (int e = tid; e < a.stage_out_n; e += 64 * W) a.stage_out_h[e] = a.stage_out_d[e];

@@ -31,7 +31,7 @@ class Fleet:
     short ttls). False: every robot keeps its first goal / path (the fleet parks), as round-2 benches ran."""
 
     def __init__(self, model, B, N, seed, dev, start=0, stream=None, solver_factory=None, schedule=None, renew=True,
-                 record_layout=None):
+                 record_layout=None, handoff=None):
         self.model, self.B, self.N = model, B, N
         self.seed, self.start = int(seed), int(start)
         self.dev = torch.device(dev)
@@ -44,6 +44,9 @@ class Fleet:
             self.solver.set_schedule(schedule)
         if record_layout is not None and "NMPC_AMD_REC_SPLIT" not in os.environ:
             self.solver.set_record_layout(record_layout)
+        # the team kernel's hand-off iteration ('auto': the measured default; None: the handle's, off)
+        if handoff is not None and hasattr(self.solver, "set_handoff") and "NMPC_AMD_HANDOFF" not in os.environ:
+            self.solver.set_handoff(-1 if handoff == "auto" else handoff)
         fl = make_fleet(model, B, seed=seed, start=start)
         self.is_path = fl["is_path"]
         t = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev, dt)  # noqa: E731
@@ -154,9 +157,14 @@ class FleetNode:
                 # beside other models' records on the same device (mixed: 5.25 -> 5.70 M it/s).
                 # Decided here, once, from the node's configuration: no other handle can flip it
                 layout = "split" if (m == "diff" and len(models) > 1 and cuda) else None
+                # the team kernel's in-block hand-off of long solves: on for a diff fleet alone on
+                # the device, where it was measured (the metric config, +5.4 %); every stream group of the fleet alike,
+                # so the robots' results do not depend on the grouping. Beside other models diff keeps the split planes,
+                # which the hand-off does not read; tric's launches are dense or split-record ones
+                handoff = "auto" if (m == "diff" and len(models) == 1 and cuda) else None
                 self.fleets.append(Fleet(m, ghi - glo, N, seed + 100 * j, self.dev, start=lo + glo, stream=stream,
                                          solver_factory=solver_factory, schedule=sched, renew=renew,
-                                         record_layout=layout))
+                                         record_layout=layout, handoff=handoff))
         self.B = sum(f.B for f in self.fleets)
         self.offs = [int(v) for v in np.cumsum([0] + [f.B for f in self.fleets])]
         self.gather = CommandGather(5, [self.B] * world, self.dev) if gather else None

@@ -23,6 +23,51 @@ L.nmpc_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 ev0.record(); f.solve(); ev1.record(); torch.cuda.synchronize()
 print("kernel ms", ev0.elapsed_time(ev1))
+C = f.solver.plan_handoff(B, "run")["iteration"]
+if C > 0:
+    # the launch ran k_sqp_rti_team_ho (NMPC_AMD_HANDOFF=C): its own stamps, first 256 blocks, per wave
+    # [0] left the team tick, [1] passed the block barrier, [2] finished its last entry, [3] entries it ran,
+    # [4] the block's flagged entries; and the resumed tick's phase stamps of the first entry each wave ran
+    KI = 64
+    hs = (ctypes.c_ulonglong * (256 * 4 * 8))()
+    hi = (ctypes.c_ulonglong * (256 * 4 * (3 + 4 * KI)))()
+    L.nmpc_debug_stamps_ho.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    assert L.nmpc_debug_stamps_ho(hs, hi) == 0
+    nb = min(256, (B + 15) // 16)
+    hs = np.frombuffer(hs, dtype=np.uint64).reshape(256, 4, 8).astype(np.int64)[:nb]
+    hi = np.frombuffer(hi, dtype=np.uint64).reshape(256, 4, 3 + 4 * KI).astype(np.int64)[:nb]
+    it = f.qp_iter.cpu().numpy()
+    left, ran = hs[:, 0, 4], hs[:, :, 3]
+    team = hs[:, :, 0].max(1) - hs[:, :, 0].min(1)   # spread of the waves' exits from the team tick
+    bar = hs[:, :, 1].min(1) - hs[:, :, 0].max(1)    # last wave in -> first wave out of the barrier
+    chain = hs[:, :, 2] - hs[:, :, 1]                # a wave's whole phase 2
+    print("hand-off C", C, "blocks stamped", nb, "robots handed over %d of %d" % (int((it >= C).sum()), B))
+    print("waves' exits from the team tick, spread: mean %.0f max %.0f cycles" % (team.mean(), team.max()))
+    print("barrier (last wave in -> first out): mean %.0f max %.0f cycles" % (bar.mean(), bar.max()))
+    print("block leftover count: mean %.2f max %d; longest wave chain: mean %.2f max %d entries" %
+          (left.mean(), left.max(), ran.max(1).mean(), ran.max()))
+    w = np.unravel_index(chain.argmax(), chain.shape)
+    print("longest phase 2: %d cycles (block %d wave %d, %d entries, block leftover %d)" %
+          (chain.max(), w[0], w[1], ran[w], left[w[0]]))
+    per, pa, pb, pm, pcd = [], [], [], [], []
+    for b in range(nb):
+        for wv in range(4):
+            if ran[b, wv] == 0:
+                continue
+            s = hi[b, wv]
+            for i in range(C, KI - 1):
+                a0, a1 = s[3 + 4 * i], s[3 + 4 * (i + 1)]  # after phase A of iterations i and i + 1
+                if a0 <= 0 or a1 <= a0 or s[4 + 4 * i] <= a0:
+                    break
+                per.append(a1 - a0)
+                pb.append(s[4 + 4 * i] - a0)
+                pm.append(s[5 + 4 * i] - s[4 + 4 * i])
+                pcd.append(s[6 + 4 * i] - s[5 + 4 * i])
+                pa.append(a1 - s[6 + 4 * i])
+    if per:
+        print("resumed iteration (A to A): mean %.0f p50 %.0f n %d; Bseg %.0f M %.0f CD %.0f A %.0f" %
+              (np.mean(per), np.median(per), len(per), np.mean(pb), np.mean(pm), np.mean(pcd), np.mean(pa)))
+    sys.exit(0)
 if hasattr(L, "nmpc_debug_stamps_pa"):
     pa = (ctypes.c_ulonglong * 256)()
     L.nmpc_debug_stamps_pa.argtypes = [ctypes.c_void_p]
